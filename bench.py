@@ -1,6 +1,6 @@
 """bench.py -- frames/s of the SAM-6D per-frame hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W            (N=1)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]            (N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]: "LM-O single object, 2048 pts, 42 templates, batch=32 bf16"):
@@ -41,8 +41,12 @@ def parse():
                     help="ranks = GPUs of this node.  Under torch.distributed.run it must equal WORLD_SIZE; started plainly with "
                          "--gpus N > 1 this process becomes the launcher: it re-executes itself as N ranks through "
                          "torch.distributed.run on 127.0.0.1 and rank 0 prints the one JSON line (default: WORLD_SIZE, else 1)")
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=_count(1), default=3, help="timed steps (at least 1)")
+    ap.add_argument("--warmup", type=_count(0), default=1, help="untimed steps before them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all; a seeded sample of the larger arrays): the inputs are seeded, so two builds run with the same "
+                         "arguments can be compared output for output")
     ap.add_argument("--frames", type=int, default=FRAMES_PER_STEP)
     ap.add_argument("--sam-chunk", type=int, default=int(os.environ.get("S6D_SAM_CHUNK", str(SAM_CHUNK))))
     ap.add_argument("--config", choices=("lmo", "fp8", "fp8mx"), default="lmo",
@@ -67,6 +71,15 @@ def parse():
     return ap.parse_args()
 
 
+def _count(least):
+    def parse(s):
+        n = int(s)
+        if n < least:
+            raise argparse.ArgumentTypeError(f"{n} < {least}")
+        return n
+    return parse
+
+
 SAM_CHUNK = 16   # frames per SAM encoder launch group: 16 x 4096 tokens per GEMM (measured on one box: chunk 8 with the
                  # recorded hipBLASLt solutions 199.0 ms / 32 frames, chunk 16 on the default heuristics 193.0, chunk 32 193.6)
 
@@ -82,6 +95,7 @@ def benched_policy():
 
 class HotPath:
     """All device state of one rank: models, replicated template data, one batch of frames."""
+    keep_outputs = False      # step() keeps what the stages returned in self.outputs (--dump-outputs)
 
     def __init__(self, device, frames, sam_chunk):
         from sam6d_amd.ism.scoring import FrameScorer
@@ -115,12 +129,12 @@ class HotPath:
     def sam_stage(self):
         from sam6d_amd.sam.image_encoder import preprocess
         nst = int(os.environ.get("S6D_SAM_STREAMS", "1"))   # measured: 1 = 2 > 4 streams (GEMMs already fill the GPU)
-        out = None
+        outs = []                                           # the image embeddings of every launch group, in frame order
         if nst <= 1:
             for i in range(0, self.F, self.chunk):
                 x = preprocess(self.sam_raw[i:i + self.chunk], 1024, out_dtype=torch.bfloat16)     # a1: Sam.preprocess
-                out = self.sam(x)                                                                  # a2-a5
-            return out
+                outs.append(self.sam(x))                                                           # a2-a5
+            return outs
         # chunks alternate between HIP streams: one chunk's latency-bound attention / LayerNorm phases run under
         # the other chunk's GEMMs
         if not hasattr(self, "_sam_streams"):
@@ -131,10 +145,10 @@ class HotPath:
         for j, i in enumerate(range(0, self.F, self.chunk)):
             with torch.cuda.stream(self._sam_streams[j % nst]):
                 x = preprocess(self.sam_raw[i:i + self.chunk], 1024, out_dtype=torch.bfloat16)
-                out = self.sam(x)
+                outs.append(self.sam(x))
         for st in self._sam_streams:
             cur.wait_stream(st)
-        return out
+        return outs
 
     @torch.no_grad()
     def ism_stage(self):
@@ -144,11 +158,11 @@ class HotPath:
         ``score`` call per frame (round 1)."""
         i = self.ism_in
         c = int(os.environ.get("S6D_ISM_CHUNK", "8"))
-        out = None
+        outs = []                                           # the scores of every launch group (every frame for c <= 0)
         if c <= 0:
             for _ in range(self.F):
-                out = self.scorer.score(i["qry_cls"], i["qry_patch"], i["masks"], i["boxes"], i["depth"], i["K"])
-            return out
+                outs.append(self.scorer.score(i["qry_cls"], i["qry_patch"], i["masks"], i["boxes"], i["depth"], i["K"]))
+            return outs
         if getattr(self, "_ism_group", None) is None or self._ism_group[0] != c:
             # every frame of a group has its own tensors in HBM and its own content (VERDICT r2: eight copies of one frame made the
             # number of selected proposals S the same for every frame): frame f is the synthetic frame with its proposals
@@ -170,9 +184,9 @@ class HotPath:
         for f0 in range(0, self.F, c):
             n = min(c, self.F - f0)
             e = f0 + n
-            out = self.scorer.score_frames(g["qry_cls"][f0:e], g["qry_patch"][f0:e], g["masks"][f0:e], g["boxes"][f0:e],
-                                           g["depth"][f0:e], K[f0:e])
-        return out
+            outs.append(self.scorer.score_frames(g["qry_cls"][f0:e], g["qry_patch"][f0:e], g["masks"][f0:e], g["boxes"][f0:e],
+                                                 g["depth"][f0:e], K[f0:e]))
+        return outs
 
     @torch.no_grad()
     def pem_stage(self):
@@ -185,10 +199,11 @@ class HotPath:
         in a running pipeline batch k's SAM encode overlaps batch k-1's scoring and pose estimation (the stages only
         depend on each other through the previous batch's outputs), and the small launch-bound ISM / PEM kernels
         fill the gaps between the SAM GEMMs.  Every stage still runs in full for every batch; the step ends when
-        all three streams have drained (S6D_BENCH_SERIAL=1 runs them back to back on one stream)."""
+        all three streams have drained (S6D_BENCH_SERIAL=1 runs them back to back on one stream).  With ``keep_outputs`` what the
+        stages return stays in ``self.outputs`` until the next step (--dump-outputs writes it)."""
         if os.environ.get("S6D_BENCH_SERIAL"):
-            self.sam_stage()
-            self.ism_stage()
+            sam = self.sam_stage()
+            ism = self.ism_stage()
             out = self.pem_stage()
         else:
             if not hasattr(self, "_streams"):
@@ -197,15 +212,17 @@ class HotPath:
             for st in self._streams:
                 st.wait_stream(cur)
             with torch.cuda.stream(self._streams[0]):
-                self.sam_stage()
+                sam = self.sam_stage()
             # the scoring loop is the only stage with host round trips (one torch.nonzero per frame, as in the
             # reference): it is enqueued LAST, so the host waits on it while the other two streams are already full
             # (measured: no difference either way -- the step is bound by the sum of kernel time, not by the host)
             out = self.pem_stage()                      # current stream
             with torch.cuda.stream(self._streams[1]):
-                self.ism_stage()
+                ism = self.ism_stage()
             for st in self._streams:
                 cur.wait_stream(st)
+        if self.keep_outputs:
+            self.outputs = {"sam": sam, "ism": ism, "pem": {k: v for k, v in out.items() if k not in self.pem_in and k != "coarse_rand_u"}}
         # fixed-width pose record per instance (68 B)
         from sam6d_amd.utils import shard
         return shard.pack_records(0, torch.arange(self.F, device=self.dev), 5, out["pred_pose_score"],
@@ -808,6 +825,38 @@ class StandInPath:
         return shard.pack_records(self.rank, torch.arange(self.F), 5, torch.full((self.F,), 0.5), R, t, 0.0).to(self.dev)
 
 
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: the arrays stay under this (64 MB with the .npy headers)
+DUMP_SAMPLE = 1 << 20          # at most this many elements per array: a seeded sample of the flat positions of a larger one
+
+
+def dump_outputs(dirname, outputs, records):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy.  Floating point arrays are written as float32
+    (float64 stays float64), integer and boolean ones as float64, which holds them exactly.  An array of more than `cap` elements
+    is written as the 1-D sample at `cap` flat positions drawn by torch.randint with seed 0 and sorted: the same positions for
+    the same shape in every run.  Names: sam_image_embeddings (every frame of the step), ism_group<k>_<key> (one set per
+    scoring launch group), pem_<key> (the keys Net.forward adds to its inputs) and pose_records (the gathered 68-byte records
+    the step ends with)."""
+    import numpy as np
+    arrays = {"pose_records": records}
+    if outputs:
+        arrays["sam_image_embeddings"] = torch.cat(outputs["sam"])
+        for k, group in enumerate(outputs["ism"]):
+            arrays.update({f"ism_group{k}_{key}": v for key, v in group.items()})
+        arrays.update({f"pem_{key}": v for key, v in outputs["pem"].items()})
+    os.makedirs(dirname, exist_ok=True)
+    cap = min(DUMP_SAMPLE, DUMP_BYTES // (8 * len(arrays)))   # 8 bytes per element at most: the bound holds by construction
+    for name, t in sorted(arrays.items()):
+        t = torch.as_tensor(t).detach()
+        flat = t.reshape(-1)
+        sampled = flat.numel() > cap
+        if sampled:
+            g = torch.Generator().manual_seed(0)
+            flat = flat[torch.randint(flat.numel(), (cap,), generator=g).sort().values.to(flat.device)]
+        a = flat.cpu().to(torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64).numpy()
+        a = a if sampled else a.reshape(tuple(t.shape))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -881,6 +930,7 @@ def main():
         _GEMM_WAVE_TILE = args.gemm_wave_tile
         _ops.set_gemm_wave_tile(args.gemm_wave_tile)
     hp = StandInPath(dev, args.frames, rank) if args.standin else HotPath(dev, args.frames, args.sam_chunk)
+    hp.keep_outputs = bool(args.dump_outputs)
 
     def barrier():
         sync()
@@ -909,6 +959,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, getattr(hp, "outputs", None), last)
 
     ms_step = dt / args.steps * 1e3
     value = world * args.frames * args.steps / dt

@@ -7,6 +7,7 @@ Run in the build container only (needs /root/reference, read-only):
     python -m oracle.gen_golden ism      # ISM scoring chain
     python -m oracle.gen_golden dinov2   # DINOv2 crops + descriptors (next row 8f-1)
     python -m oracle.gen_golden sam_decoder   # SAM prompt encoder + mask decoder (next row 8f-2)
+    python -m oracle.gen_golden pn2_ref  # the reference's PointNet++ kernels (oracle/_ref) on tests/test_oracle_pn2_ref.py's inputs
 
 PEM and ISM must run in separate processes (both trees own top-level names).  The
 reference modules are imported unmodified through oracle/refharness.py; weights and inputs
@@ -408,7 +409,8 @@ def gen_sam_transforms():
 
 
 def gen_sam_state_dict():
-    """state_dict keys / shapes of the reference's three Sam builds (build_sam.py run unmodified on the meta device)."""
+    """state_dict keys / shapes of the reference's three Sam builds (build_sam.py run unmodified on the meta device), and the
+    surface tests/test_host_build_sam.py compares (sam_surface.json: with dtypes, the "default" entry and the model attributes)."""
     import json
     mod = rh.sam_builder()
     rec = {}
@@ -419,6 +421,20 @@ def gen_sam_state_dict():
     with open(os.path.join(OUT, "sam_state_dict.json"), "w") as f:
         json.dump(rec, f, separators=(",", ":"))
     print("sam_state_dict.json", {k: len(v) for k, v in rec.items()})
+    from tests.test_host_build_sam import sam_surface
+    surf = {name: sam_surface(mod.sam_model_registry, name) for name in ("vit_h", "vit_l", "vit_b", "default")}
+    with open(os.path.join(OUT, "sam_surface.json"), "w") as f:
+        json.dump(surf, f, separators=(",", ":"))
+    print("sam_surface.json", {k: len(v["state"]) for k, v in surf.items()})
+
+
+def gen_pn2_ref():
+    """Outputs of the reference's own PointNet++ kernels (oracle/build_ref.py -> oracle/_ref) on every input of
+    tests/test_oracle_pn2_ref.py, which compares pn2_oracle.c with them on hosts without the reference tree."""
+    from tests.test_oracle_pn2_ref import golden_arrays, reference_outputs
+    rec = golden_arrays(reference_outputs())
+    np.savez_compressed(os.path.join(OUT, "pn2_ref.npz"), **rec)
+    print("pn2_ref.npz", len(rec), "arrays")
 
 
 def gen_pem_pre():
@@ -1219,4 +1235,4 @@ if __name__ == "__main__":
     if sys.argv[1] in ("frame_ism", "frame_pem", "frame_e2e_ism", "frame_e2e_pem"):
         {"frame_ism": gen_frame_ism, "frame_pem": gen_frame_pem, "frame_e2e_ism": gen_frame_e2e_ism, "frame_e2e_pem": gen_frame_e2e_pem}[sys.argv[1]](sys.argv[2])
         sys.exit(0)
-    {"frame": gen_frame, "frame_e2e": gen_frame_e2e, "frame_e2e_pose": gen_frame_e2e_pose, "frame_e2e_nms": gen_frame_e2e_nms, "pem": gen_pem, "pem_b32": gen_pem_b32, "pem_wc": gen_pem_wc, "example": gen_example, "sam": gen_sam, "ism": gen_ism, "dinov2": gen_dinov2, "sam_decoder": gen_sam_decoder, "handoff": gen_handoff, "pem_pre": gen_pem_pre, "pem_results": gen_pem_results, "detections_ops": gen_detections_ops, "sam_transforms": gen_sam_transforms, "sam_state_dict": gen_sam_state_dict}[sys.argv[1]]()
+    {"frame": gen_frame, "frame_e2e": gen_frame_e2e, "frame_e2e_pose": gen_frame_e2e_pose, "frame_e2e_nms": gen_frame_e2e_nms, "pem": gen_pem, "pem_b32": gen_pem_b32, "pem_wc": gen_pem_wc, "example": gen_example, "sam": gen_sam, "ism": gen_ism, "dinov2": gen_dinov2, "sam_decoder": gen_sam_decoder, "handoff": gen_handoff, "pem_pre": gen_pem_pre, "pem_results": gen_pem_results, "detections_ops": gen_detections_ops, "sam_transforms": gen_sam_transforms, "sam_state_dict": gen_sam_state_dict, "pn2_ref": gen_pn2_ref}[sys.argv[1]]()

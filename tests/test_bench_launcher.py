@@ -52,3 +52,21 @@ def test_single_rank_default_and_world_mismatch():
     assert d["n_gpus"] == 1 and d["gathered_rows"] == 2
     r = _run(["--gpus", "4", "--standin"], env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_writes_the_last_step_the_same_every_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's arrays as DIR/<name>.npy in float32 / float64, equal from run to run; --steps is
+    the number of timed steps and must be at least 1."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "3", "--standin", "--dump-outputs", str(tmp_path / run)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        assert os.listdir(tmp_path / run) == ["pose_records.npy"]
+        dumps.append(np.load(tmp_path / run / "pose_records.npy"))
+        assert dumps[-1].dtype in (np.float32, np.float64) and dumps[-1].shape == (6, 17)
+    assert np.array_equal(dumps[0], dumps[1]) and dumps[0][:, 0].tolist() == [0, 0, 0, 1, 1, 1]
+    r = _run(["--steps", "0", "--standin"])
+    assert r.returncode != 0 and "--steps" in r.stderr

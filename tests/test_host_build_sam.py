@@ -1,7 +1,11 @@
 """The Sam container / builders keep the reference's checkpoint surface: same state_dict keys, shapes and dtypes as
 segment_anything/build_sam.py run unmodified (both built on the meta device: no memory, no arithmetic), for all three
-encoder sizes; and the segmentor plugin keeps the reference's constructor."""
+encoder sizes; and the segmentor plugin keeps the reference's constructor.  The reference's surface is stored in
+tests/golden/sam_surface.json (oracle/gen_golden.py sam_state_dict); where the reference tree is there, it is built live as well
+and must still equal the stored one."""
 import inspect
+import json
+import os
 
 import pytest
 import torch
@@ -10,24 +14,27 @@ from oracle import refharness as rh
 from sam6d_amd.ism import segmentor
 from sam6d_amd.sam import build_sam
 
-needs_ref = pytest.mark.skipif(not rh.available(), reason="reference tree not mounted")
+
+def sam_surface(registry, name):
+    """What a checkpoint and a caller see of registry[name]() built on the meta device: state_dict entries in order (key, shape,
+    dtype), the encoder's input size, mask threshold, image format, the shape of the non-persistent pixel_mean buffer and the
+    training flag."""
+    with torch.device("meta"):
+        m = registry[name]()
+    return dict(state=[[k, list(v.shape), str(v.dtype)] for k, v in m.state_dict().items()], img_size=m.image_encoder.img_size,
+                mask_threshold=m.mask_threshold, image_format=m.image_format, pixel_mean=list(m.pixel_mean.shape), training=m.training)
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["vit_h", "vit_l", "vit_b", "default"])
 def test_state_dict_surface_equals_the_reference(name):
-    ref_mod = rh.sam_builder()
-    with torch.device("meta"):
-        ours = build_sam.sam_model_registry[name]()
-        ref = ref_mod.sam_model_registry[name]()
-    a = {k: (tuple(v.shape), v.dtype) for k, v in ours.state_dict().items()}
-    b = {k: (tuple(v.shape), v.dtype) for k, v in ref.state_dict().items()}
-    assert a == b and len(a) > 300
-    assert list(ours.state_dict()) == list(ref.state_dict())                   # same order as well
-    assert ours.image_encoder.img_size == ref.image_encoder.img_size == 1024
-    assert ours.mask_threshold == ref.mask_threshold and ours.image_format == ref.image_format
-    assert "pixel_mean" not in a and tuple(ours.pixel_mean.shape) == tuple(ref.pixel_mean.shape)   # non-persistent buffers
-    assert not ours.training
+    with open(os.path.join(os.path.dirname(__file__), "golden", "sam_surface.json")) as f:
+        ref = json.load(f)[name]
+    if rh.available():
+        assert sam_surface(rh.sam_builder().sam_model_registry, name) == ref, "the reference no longer gives tests/golden/sam_surface.json"
+    ours = sam_surface(build_sam.sam_model_registry, name)
+    assert ours == ref and len(ours["state"]) > 300                       # keys, shapes, dtypes, order
+    assert ours["img_size"] == 1024 and not ours["training"]
+    assert "pixel_mean" not in [k for k, _, _ in ours["state"]]             # non-persistent buffer
 
 
 @pytest.mark.parametrize("name", ["vit_h", "vit_l", "vit_b"])

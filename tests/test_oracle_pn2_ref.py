@@ -1,11 +1,17 @@
 """Pins oracle/pn2_oracle.c (the comparand of the device PointNet++ kernels, rows a13 / a19) to the REFERENCE'S OWN kernels:
-oracle/build_ref.py compiles sampling_gpu.cu / ball_query_gpu.cu / group_points_gpu.cu from /root/reference for the host
-(oracle/_ref/, emulated CUDA runtime) and every case of tests/test_gpu_pn2.py is run through both, bit for bit.
+oracle/build_ref.py compiles sampling_gpu.cu / ball_query_gpu.cu / group_points_gpu.cu from the reference tree for the host
+(oracle/_ref/, emulated CUDA runtime) and every case of tests/test_gpu_pn2.py is run through both, bit for bit.  The reference
+kernels' outputs for these cases are stored in tests/golden/pn2_ref.npz (oracle/gen_golden.py pn2_ref; the large ones as a
+SHA-256 of their bits), so the comparison runs
+on every host; where oracle/_ref is built (or the reference tree is there to build it) the live kernels are run as well and must
+still equal the stored outputs.
 
 What the reference source does not decide is the contraction of  a*a + b*b + c*c  (nvcc --fmad): the restatement carries three
 spellings and is held to the two a host compiler can produce from the unmodified source (none; LLVM's).  The third -- nvcc's
 default, fma(c,c, fma(b,b, a*a)), the one the product kernels spell -- differs from them only in the rounding of one product;
 `test_where_the_contraction_spellings_diverge` measures how often that reaches an OUTPUT index."""
+import functools
+import hashlib
 import os
 
 import numpy as np
@@ -14,11 +20,10 @@ import torch
 
 from oracle import pn2 as opn2
 from oracle import pn2_ref
+from tests import util
 from tests.test_gpu_pn2 import _cloud
 
-pytestmark = pytest.mark.skipif(not (pn2_ref.available("off") or os.path.isdir(os.environ.get("S6D_REFERENCE_ROOT", "/root/reference"))),
-                                reason="oracle/_ref is built in the build container (python -m oracle.build_ref)")
-
+LIVE = (pn2_ref.available("off") and pn2_ref.available("fast")) or os.path.isdir(os.environ.get("S6D_REFERENCE_ROOT", "/root/reference"))
 PAIRS = [(2, "off"), (1, "fast")]          # (pn2_oracle.c contraction mode, _ref build)
 
 FPS_CASES = [(2, 2048, 196, False), (3, 2048, 196, True), (1, 700, 64, True), (2, 64, 64, False), (1, 1, 1, False),
@@ -26,13 +31,88 @@ FPS_CASES = [(2, 2048, 196, False), (3, 2048, 196, True), (1, 700, 64, True), (2
 BQ_CASES = [(2, 2048, 2048, 0.1, 32), (2, 2048, 2048, 0.2, 64), (1, 300, 50, 0.2, 16), (1, 100, 7, 0.5, 128), (1, 5000, 100, 0.05, 8)]
 
 
+def _fps_input(B, N, dup):
+    return _cloud(B, N, 100 + N, dup)
+
+
+def _bq_input(B, N, M):
+    x = _cloud(B, N, 7 + N, dup=True)
+    return (x[:, :M].contiguous() if M <= N else _cloud(B, M, 3)), x
+
+
+def _tie_input():
+    y = torch.zeros(1, 600, 3)
+    y[0, 520] = 1.0
+    y[0, 9] = 1.0
+    return y
+
+
+def _gather_group_input():
+    g = torch.Generator().manual_seed(3)
+    feats = torch.randn(3, 37, 500, generator=g)
+    idx = torch.randint(0, 500, (3, 196), generator=g, dtype=torch.int32)
+    gi = torch.randint(0, 500, (3, 60, 16), generator=g, dtype=torch.int32)
+    return feats, idx, gi
+
+
+def reference_outputs():
+    """{name: output} of the reference kernels (oracle/_ref) on every input of this module: what tests/golden/pn2_ref.npz holds
+    (written by oracle/gen_golden.py pn2_ref)."""
+    out = {}
+    for _, v in PAIRS:
+        for B, N, M, dup in FPS_CASES:
+            out[f"fps_{B}_{N}_{M}_{int(dup)}_{v}"] = pn2_ref.furthest_point_sampling(_fps_input(B, N, dup), M, v)
+        out[f"fps_temp_{v}"] = pn2_ref.furthest_point_sampling(_cloud(2, 2048, 77), 196, v, with_temp=True)[1]
+        out[f"fps_tie_{v}"] = pn2_ref.furthest_point_sampling(_tie_input(), 3, v)
+        for B, N, M, r, ns in BQ_CASES:
+            q, x = _bq_input(B, N, M)
+            out[f"bq_{B}_{N}_{M}_{r}_{ns}_{v}"] = pn2_ref.ball_query(q, x, r, ns, v)
+            out[f"bq_far_{B}_{N}_{M}_{r}_{ns}_{v}"] = pn2_ref.ball_query(torch.full((1, 4, 3), 50.0), x[:1], 0.2, 8, v)
+    feats, idx, gi = _gather_group_input()
+    out["gather"] = pn2_ref.gather_points(feats, idx)
+    out["group"] = pn2_ref.group_points(feats, gi)
+    return out
+
+
+SMALL = 1024        # outputs of at most this many elements are stored whole; a larger one as the SHA-256 of its dtype, shape and bytes
+
+
+def fingerprint(t):
+    a = np.ascontiguousarray(t.numpy())
+    return np.frombuffer(hashlib.sha256(f"{a.dtype}{a.shape}".encode() + a.tobytes()).digest(), np.uint8)
+
+
+def golden_arrays(outputs):
+    """What tests/golden/pn2_ref.npz stores of reference_outputs(): `name` -> the array, or `name`_sha256 -> its fingerprint."""
+    return {(k if v.numel() <= SMALL else k + "_sha256"): (v.numpy() if v.numel() <= SMALL else fingerprint(v)) for k, v in outputs.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _golden():
+    return util.golden("pn2_ref.npz")
+
+
+def _equals_reference(name, t, live):
+    """`t` has the bits of the reference kernels' output `name` as tests/golden/pn2_ref.npz holds it (whole or as a fingerprint);
+    where the kernels are at hand, `live()` runs them and must give the same bits."""
+    g = _golden()
+
+    def same(x):
+        if name + "_sha256" in g:
+            return np.array_equal(fingerprint(x), g[name + "_sha256"])
+        return torch.equal(x, torch.from_numpy(g[name]))
+    if LIVE:
+        assert same(live()), f"{name}: the reference kernel no longer gives tests/golden/pn2_ref.npz"
+    return same(t)
+
+
 @pytest.mark.parametrize("mode,variant", PAIRS)
 @pytest.mark.parametrize("B,N,M,dup", FPS_CASES)
 def test_fps_restatement_equals_reference_kernel(B, N, M, dup, mode, variant):
-    x = _cloud(B, N, 100 + N, dup)
+    x = _fps_input(B, N, dup)
     with opn2.contraction(mode):
         mine = opn2.furthest_point_sampling(x, M)
-    assert torch.equal(mine, pn2_ref.furthest_point_sampling(x, M, variant))
+    assert _equals_reference(f"fps_{B}_{N}_{M}_{int(dup)}_{variant}", mine, lambda: pn2_ref.furthest_point_sampling(x, M, variant))
 
 
 def test_distance_bits_follow_the_contraction():
@@ -45,7 +125,8 @@ def test_distance_bits_follow_the_contraction():
         with opn2.contraction(mode):
             temps[mode] = opn2.furthest_point_sampling_with_temp(x, 196)[1]
     for mode, variant in PAIRS:
-        assert torch.equal(temps[mode], pn2_ref.furthest_point_sampling(x, 196, variant, with_temp=True)[1])
+        assert _equals_reference(f"fps_temp_{variant}", temps[mode],
+                                 lambda: pn2_ref.furthest_point_sampling(x, 196, variant, with_temp=True)[1])
     assert not torch.equal(temps[0], temps[1]) and not torch.equal(temps[0], temps[2]) and not torch.equal(temps[1], temps[2])
     assert (temps[0] - temps[2]).abs().max() <= 2e-7 * temps[2].abs().max()
 
@@ -53,33 +134,29 @@ def test_distance_bits_follow_the_contraction():
 def test_fps_tie_break_of_the_reference_tree():
     """Equal distances: the reference's shared-memory tree keeps the lower SLOT (bit-reversed order of thread ids), not the
     lower index -- the rule the device kernel's 64-bit keys encode (tests/test_gpu_pn2.py::test_fps_tie_break_rule)."""
-    y = torch.zeros(1, 600, 3)
-    y[0, 520] = 1.0
-    y[0, 9] = 1.0
+    y = _tie_input()
     for mode, variant in PAIRS:
         with opn2.contraction(mode):
-            assert torch.equal(opn2.furthest_point_sampling(y, 3), pn2_ref.furthest_point_sampling(y, 3, variant))
+            assert _equals_reference(f"fps_tie_{variant}", opn2.furthest_point_sampling(y, 3),
+                                     lambda: pn2_ref.furthest_point_sampling(y, 3, variant))
 
 
 @pytest.mark.parametrize("mode,variant", PAIRS)
 @pytest.mark.parametrize("B,N,M,r,ns", BQ_CASES)
 def test_ball_query_restatement_equals_reference_kernel(B, N, M, r, ns, mode, variant):
-    x = _cloud(B, N, 7 + N, dup=True)
-    q = x[:, :M].contiguous() if M <= N else _cloud(B, M, 3)
+    q, x = _bq_input(B, N, M)
     with opn2.contraction(mode):
         mine = opn2.ball_query(q, x, r, ns)
-    assert torch.equal(mine, pn2_ref.ball_query(q, x, r, ns, variant))
+    assert _equals_reference(f"bq_{B}_{N}_{M}_{r}_{ns}_{variant}", mine, lambda: pn2_ref.ball_query(q, x, r, ns, variant))
     far = torch.full((1, 4, 3), 50.0)
-    assert torch.equal(pn2_ref.ball_query(far, x[:1], 0.2, 8, variant), torch.zeros(1, 4, 8, dtype=torch.int32))
+    assert _equals_reference(f"bq_far_{B}_{N}_{M}_{r}_{ns}_{variant}", torch.zeros(1, 4, 8, dtype=torch.int32),
+                             lambda: pn2_ref.ball_query(far, x[:1], 0.2, 8, variant))
 
 
 def test_gather_and_group_equal_reference_kernels():
-    g = torch.Generator().manual_seed(3)
-    feats = torch.randn(3, 37, 500, generator=g)
-    idx = torch.randint(0, 500, (3, 196), generator=g, dtype=torch.int32)
-    assert torch.equal(opn2.gather_points(feats, idx), pn2_ref.gather_points(feats, idx))
-    gi = torch.randint(0, 500, (3, 60, 16), generator=g, dtype=torch.int32)
-    assert torch.equal(opn2.group_points(feats, gi), pn2_ref.group_points(feats, gi))
+    feats, idx, gi = _gather_group_input()
+    assert _equals_reference("gather", opn2.gather_points(feats, idx), lambda: pn2_ref.gather_points(feats, idx))
+    assert _equals_reference("group", opn2.group_points(feats, gi), lambda: pn2_ref.group_points(feats, gi))
 
 
 def test_where_the_contraction_spellings_diverge():
