@@ -6,6 +6,7 @@ import pytest
 from tests import test_gpu_dinov2 as TD
 from tests import test_gpu_sam as TS
 from tests import test_gpu_sam_decoder as T
+from tests import test_gpu_sam_decoder_production as TP
 
 
 def test_mask_post_kernel_on_the_emulator(emu):
@@ -169,3 +170,83 @@ def test_token_side_kernels_on_the_emulator(emu):
 
 def test_token_side_folds_on_the_emulator(emu):
     T.test_token_side_kernels_with_the_folds_inside(2, 5)
+
+
+# ---- the production-shape bodies of tests/test_gpu_sam_decoder_production.py at N = 4096 (B <= 2): every wave of img2tok_kernel /
+# upscale_heads_kernel walks four strips, the token->image kernels run their full-length token loops, the NMS scan uses its 65th word
+EMU_B, EMU_N = 2, 4096
+
+
+@pytest.mark.parametrize("T,shared", [(5, True), (7, False), (8, True), (8, False)])
+def test_img2tok_multi_strip_on_the_emulator(emu, T, shared):
+    TP.img2tok_case(EMU_B, EMU_N, T, shared, dev="cpu", invariance=False)
+
+
+@pytest.mark.parametrize("T,shared,use_pe", [(5, False, True), (7, True, True), (8, False, False)])
+def test_img2tok_raw_multi_strip_on_the_emulator(emu, T, shared, use_pe):
+    TP.img2tok_raw_case(EMU_B, EMU_N, T, shared, use_pe, dev="cpu", invariance=False)
+
+
+@pytest.mark.parametrize("T,shared", [(7, False), (5, True)])
+def test_tok2img_full_length_on_the_emulator(emu, T, shared):
+    TP.tok2img_case(EMU_B, EMU_N, T, shared, dev="cpu", invariance=False)
+
+
+@pytest.mark.parametrize("T,shared,use_pe", [(7, False, True), (8, True, True), (5, False, False)])
+def test_tok2img_raw_full_length_on_the_emulator(emu, T, shared, use_pe):
+    TP.tok2img_raw_case(EMU_B, EMU_N, T, shared, use_pe, dev="cpu", invariance=False)
+
+
+@pytest.mark.parametrize("T,shared,use_pe", [(7, False, True), (8, True, True), (5, False, False)])
+def test_tok2img_raw_core_full_length_on_the_emulator(emu, T, shared, use_pe):
+    TP.tok2img_raw_core_case(EMU_B, EMU_N, T, shared, use_pe, dev="cpu", invariance=False)
+
+
+@pytest.mark.parametrize("M", [1, 3, 4])
+def test_upscale_heads_multi_strip_on_the_emulator(emu, M):
+    TP.upscale_heads_case(EMU_B, 64, M, dev="cpu", invariance=False)
+
+
+@pytest.mark.parametrize("B,T", [(2, 5), (1, 8)])
+def test_token_kernels_production_body_on_the_emulator(emu, B, T):
+    TP.tokens_case(B, T, dev="cpu", invariance=False)
+
+
+def test_token_kernels_with_folds_at_4096_tokens_on_the_emulator(emu):
+    TP.tokens_fold_case(EMU_B, EMU_N, 7, dev="cpu", invariance=False)
+
+
+def test_nms_word_boundaries_on_the_emulator(emu):
+    TP.nms_boundary_case(4097, dev="cpu")
+
+
+def _launch_grid_x(fn, nstrip):
+    """Workgroups along x of a strip-loop kernel, from its launch formula in csrc/s6d_samdec.hip (`gx = nstrip >= A ? G : (nstrip + 3)
+    / 4` in the entry point `fn`).  A launch formula of another form fails here: the coverage below must then be re-derived."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sam6d_amd", "csrc", "s6d_samdec.hip")).read()
+    body = src[src.index(fn):]
+    m = re.search(r"const int gx = nstrip >= (\d+) \? (\d+) : \(nstrip \+ 3\) / 4;", body)
+    assert m, f"{fn}: launch formula changed"
+    a, gx = int(m.group(1)), int(m.group(2))
+    return gx if nstrip >= a else (nstrip + 3) // 4
+
+
+def test_production_shapes_walk_several_strips_per_wave():
+    """The N = 4096 / h = w = 64 cases of tests/test_gpu_sam_decoder_production.py (and their emulator runs above) make every wave of
+    img2tok_kernel and upscale_heads_kernel walk more than one strip (strip = blockIdx.x * 4 + wave, step gridDim.x * 4), so the
+    loop-carried part (the next strip's prefetch, LDS reuse, the strip stride) is compared against the reference; at the N = 256 /
+    h = w = 8 sizes of tests/test_gpu_sam_decoder.py each wave does one strip."""
+    def strips_per_wave(fn, nstrip):
+        waves = 4 * _launch_grid_x(fn, nstrip)
+        return -(-nstrip // waves), nstrip // waves
+
+    from tests import test_gpu_sam_decoder_production as P
+    assert P.N_PROD == EMU_N == 4096
+    most, least = strips_per_wave("img2tok_launch", P.N_PROD // 16)               # nstrip = N / 16
+    assert least >= 2 and most == 4, (most, least)
+    most, least = strips_per_wave("s6d_samdec_upscale_heads_bf16", 64 * 64 // 16 * 4)  # nstrip = h w / 16 * 4
+    assert least >= 2 and most == 4, (most, least)
+    assert strips_per_wave("img2tok_launch", 256 // 16) == (1, 1)                   # the toy sizes: one strip per wave
+    assert strips_per_wave("s6d_samdec_upscale_heads_bf16", 8 * 8 // 16 * 4) == (1, 1)
