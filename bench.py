@@ -1,6 +1,6 @@
 """bench.py -- frames/s of the SAM-6D per-frame hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]            (N=1)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]: "LM-O single object, 2048 pts, 42 templates, batch=32 bf16"):
@@ -15,6 +15,9 @@ Inputs are resident in HBM before the timed region; weights are seeded-random (n
 reachable offline), results therefore meaningless but the arithmetic is the full model.
 Frames shard across ranks with no data-path collective (weak scaling); the only RCCL traffic is the
 final all_gather of the fixed-width pose records, inside the timed region.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the JSON line.  --full adds the side
+measurements after the timed steps (rank 0, minutes): stage split, PEM extractor dtypes, per-kernel rooflines, host-input
+rate, the fp8 configurations, the whole-frame and sharded blocks and the CPU baseline, as extra keys of the same line.
 """
 import argparse
 import json
@@ -57,13 +60,17 @@ def parse():
                          "form everywhere, 128 = four-wave form wherever it applies -- for same-box A/B runs")
     ap.add_argument("--strict", action="store_true",
                     help="sam6d_amd.policy strict mode: a library (rocBLAS / ATen) branch of a module on a CUDA tensor raises, naming the failed guard")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, the side measurements too (rank 0, minutes): stage split, PEM extractor dtypes, "
+                         "per-kernel rooflines, host-input rate, fp8 configurations, whole-frame and sharded blocks, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` block")
     ap.add_argument("--cpu-baseline-only", action="store_true")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip the whole-frame `pipeline` block (all five models)")
-    ap.add_argument("--no-fp8", action="store_true", help="skip the `configs.fp8` block (BASELINE configs[4] measured next to the headline)")
+    ap.add_argument("--no-pipeline", action="store_true", help="with --full: skip the whole-frame `pipeline` block (all five models)")
+    ap.add_argument("--no-fp8", action="store_true",
+                    help="with --full: skip the `configs.fp8` block (BASELINE configs[4] measured next to the headline)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="the timed steps only (no stage split, no per-kernel rows, no fp8 / whole-frame / CPU blocks): the target of the "
-                         "rocprofv3 kernel-statistics passes, so that their shares are the step's and not the side measurements'")
+                    help="the timed steps only, even with --full: what a run without --full does (the target of the rocprofv3 "
+                         "kernel-statistics passes, so that their shares are the step's and not the side measurements')")
     ap.add_argument("--standin", action="store_true",
                     help="TEST INFRASTRUCTURE (tests/test_bench_launcher.py): stand-in stages on the CPU over gloo, to exercise the "
                          "launcher, the barriers, the record gather and the JSON line on a host without GPUs; the line it prints "
@@ -968,19 +975,19 @@ def main():
     # the benched step is expected to take none
     lib_hits = {} if args.standin else {f"{s}:{g}": n for (s, g), n in __import__("sam6d_amd.policy").policy.library_branch_hits().items()}
     if dist is not None:
-        # the process group ends HERE, with every rank present: rank 0 goes on alone into minutes of side measurements, and a
-        # destroy_process_group issued after the other ranks have exited may wait on them
+        # the process group ends HERE, with every rank present: with --full rank 0 goes on alone into minutes of side measurements,
+        # and a destroy_process_group issued after the other ranks have exited may wait on them
         dist.barrier()
         dist.destroy_process_group()
         dist = None
 
-    # stage breakdown + roofline of the dominant stage (rank 0 only; outside the timed region)
+    # --full: stage breakdown + roofline of the dominant stage and the other side blocks (rank 0 only; outside the timed region)
     extra = {"library_branches_in_the_timed_steps": lib_hits, "strict": bool(args.strict)}
     if args.standin:
         extra["standin"] = True
         extra["gathered_rows"] = int(last.shape[0])
         extra["gathered_ranks"] = sorted({int(v) for v in last[:, 0].tolist()})
-    elif rank == 0 and not args.no_extras:
+    elif rank == 0 and args.full and not args.no_extras:
         try:
             _extras(extra, hp, dev, args, world)
         except Exception as e:  # noqa: BLE001  (the headline line must come out even if a side measurement fails)

@@ -70,3 +70,15 @@ def test_dump_outputs_writes_the_last_step_the_same_every_run(tmp_path):
     assert np.array_equal(dumps[0], dumps[1]) and dumps[0][:, 0].tolist() == [0, 0, 0, 1, 1, 1]
     r = _run(["--steps", "0", "--standin"])
     assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_side_measurements_only_with_full():
+    """A plain run is set-up, warm-up, the timed steps and the JSON line; the side measurements (stage split, rooflines, fp8 /
+    whole-frame blocks, CPU baseline) come with --full only.  The stand-in path accepts --full and prints the same line."""
+    code = "import sys; sys.argv[0] = 'bench.py'; import bench; a = bench.parse(); print(a.full, a.no_extras)"
+    for extra, want in (([], "False False"), (["--full"], "True False")):
+        r = subprocess.run([sys.executable, "-c", code] + extra, capture_output=True, text=True, timeout=120, cwd=ROOT)
+        assert r.returncode == 0 and r.stdout.split() == want.split(), r.stderr[-2000:]
+    r = _run(["--steps", "1", "--warmup", "0", "--frames", "2", "--standin", "--full"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _line(r.stdout)["gathered_rows"] == 2
