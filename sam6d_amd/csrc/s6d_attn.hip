@@ -185,8 +185,12 @@ __device__ __forceinline__ bool token_offset(const AttnParams &p, int b, int wy,
   }
   const int ty = div_S(p, t), tx = t - ty * p.S;
   const int y = wy * p.ws + ty, x = wx * p.ws + tx;
-  off = ((size_t)(b * p.H + min(y, p.H - 1)) * p.W + min(x, p.W - 1));
-  return (y < p.H) && (x < p.W) && (t < p.T);
+  const bool in = (y < p.H) && (x < p.W) && (t < p.T);
+  // sequences (no qkv_bias: s6d_seq_attention_*) stage a slot past the end from their OWN first token, which load_chunk then reads:
+  // the padded query rows of the last strip take part in process_tile's wave-wide rescale vote, so their values reach the real rows'
+  // rounding; taken from another sequence of the launch, they made a sequence's result depend on its neighbours
+  off = (in || p.qkv_bias) ? ((size_t)(b * p.H + min(y, p.H - 1)) * p.W + min(x, p.W - 1)) : (size_t)b * p.H * p.W;
+  return in;
 }
 
 // 8 consecutive head-dim elements [d0, d0+8) of q/k/v (which = 0/1/2) for a token slot.  Branch-free on
@@ -198,7 +202,7 @@ __device__ __forceinline__ uint4 load_chunk(const AttnParams &p, int which, int 
   const int C = p.nh * HD;
   const int dc = d0 < HD ? d0 : HD - 8;
   const u16 *a = qkv_at(p, tok, which, head) + dc;
-  const u16 *bsrc = p.qkv_bias + (size_t)which * C + head * HD + dc;
+  const u16 *bsrc = p.qkv_bias ? p.qkv_bias + (size_t)which * C + head * HD + dc : a;       // (sequences: see token_offset)
   const uint4 v = *reinterpret_cast<const uint4 *>(valid ? a : bsrc);
   return d0 < HD ? v : make_uint4(0, 0, 0, 0);
 }
@@ -2032,7 +2036,7 @@ extern "C" int S6D_SEQ_ATTENTION_STRIDED(const void *qkv, long tok_stride, long 
   if (!qkv || !out || ((uintptr_t)qkv & 15)) return S6D_EINVAL;
   // a 1 x N "image" attended as ONE all-resident window of N key slots, no positional bias
   AttnParams p;
-  p.qkv = (const u16 *)qkv; p.qkv_bias = (const u16 *)qkv;        // never read: every slot < N is in-image
+  p.qkv = (const u16 *)qkv; p.qkv_bias = nullptr;                 // slots past N read their sequence's first token (token_offset)
   p.rel_h = nullptr; p.rel_w = nullptr; p.out = (u16 *)out;
   p.B = B; p.H = 1; p.W = N; p.nh = num_heads; p.ws = N;
   p.S = N; p.T = N; p.nwx = 1; p.nwy = 1; p.LT = 16;

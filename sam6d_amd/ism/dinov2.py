@@ -371,7 +371,8 @@ class _FrameBatcher:
     (measured: 25.6 ms per 128 crops alone, 21.9 ms in batches of 255; inside a frame group the gain shrinks to 0.7 ms per frame, the
     full batches running at the socket's power limit).  A full batch is launched as soon as 255 crops have accumulated -- the device
     then has descriptor work queued while the host prepares the next frame's proposals -- the rest at ``finish``.  A row of
-    a batch does not depend on its neighbours in any kernel of the path: the values are those of per-frame calls."""
+    a batch does not depend on its neighbours in any kernel of the path: the values are those of per-frame calls
+    (tests/test_gpu_dinov2_production.py::test_descriptor_path_is_batch_invariant)."""
 
     FULL = 255                                                            # 255 x 257 token rows = 256 row tiles exactly
 
