@@ -7,6 +7,9 @@ test_bop.py:123-185.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \\
         tools/run_sharded.py --frames 256 --group 8 --out results/ycbv.csv
 
+`--assign dynamic`: instead of the fixed split (rank r takes frames r, r + W, ...) the ranks claim groups of --group consecutive
+frames from a counter in a TCPStore rank 0 hosts on --claim-port (utils/shard.run_sharded); `--no-prefetch` claims only when idle.
+
 Synthetic split (there is no dataset in the image): --frames frames of 480 x 640 RGB-D whose proposal count P (32..128) and
 instance count K (2..16) vary from frame to frame, seeded by (scene_id, im_id) -- the imbalance a real split has.  Weights are
 seeded (no checkpoint offline).  Prints one JSON line: frames/s of the whole job, per-rank busy seconds / frames / instances
@@ -96,7 +99,12 @@ def measure_world1(dev, frames=24, group=8):
     costs = one["group_seconds"]
     balance = {"frames": len(costs), "frame_ms_min": round(min(costs) * 1e3, 1), "frame_ms_max": round(max(costs) * 1e3, 1),
                "world8_round_robin": round(shard.assignment_efficiency(costs, 8, "round_robin"), 3),
-               "world8_cost_sorted_bound": round(shard.assignment_efficiency(costs, 8, "lpt"), 3)}
+               "world8_cost_sorted_bound": round(shard.assignment_efficiency(costs, 8, "lpt"), 3),
+               # run_sharded(assignment="dynamic") replayed on the same costs: claim when idle, claim one group ahead (what the
+               # prefetch thread needs), claim when idle in groups of 8 consecutive frames
+               "world8_dynamic": round(shard.assignment_efficiency(costs, 8, "dynamic", group_size=1, lookahead=0), 3),
+               "world8_dynamic_lookahead1": round(shard.assignment_efficiency(costs, 8, "dynamic", group_size=1, lookahead=1), 3),
+               "world8_dynamic_group8": round(shard.assignment_efficiency(costs, 8, "dynamic", group_size=8, lookahead=0), 3)}
     return {"load_wait_ms_per_frame_behind_the_prefetch_thread": round(res["load_wait_seconds"] / frames * 1e3, 2),
             "world8_balance_from_world1_frame_times": balance,"workload": f"{frames} synthetic 480x640 frames, proposals per frame {min(p for p, _ in shapes)}..{max(p for p, _ in shapes)} "
                         f"(mean {sum(p for p, _ in shapes) / frames:.0f}), instances per frame {min(k for _, k in shapes)}..{max(k for _, k in shapes)} "
@@ -113,6 +121,10 @@ def main(argv=None):
     ap.add_argument("--dataset", default="ycbv")
     ap.add_argument("--stand-in", action="store_true")
     ap.add_argument("--fixed-time", type=float, default=None)
+    ap.add_argument("--assign", choices=("static", "dynamic"), default="static",
+                    help="static: rank r of W takes frames r, r + W, ...; dynamic: ranks claim groups of consecutive frames from a shared counter")
+    ap.add_argument("--no-prefetch", action="store_true", help="load a group's frames on the compute thread (dynamic: claim only when idle)")
+    ap.add_argument("--claim-port", type=int, default=0, help="port of the --assign dynamic counter store on MASTER_ADDR (default MASTER_PORT + 1)")
     a = ap.parse_args(argv)
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -126,6 +138,11 @@ def main(argv=None):
         backend = "nccl"
     if world > 1:
         dist.init_process_group(backend, rank=rank, world_size=world)
+    store = None
+    if a.assign == "dynamic" and world > 1:
+        # the claim counter: a store of its own beside the rendezvous one, hosted by rank 0 (a fetch-and-add per group, no frame data)
+        store = dist.TCPStore(os.environ.get("MASTER_ADDR", "127.0.0.1"), a.claim_port or int(os.environ["MASTER_PORT"]) + 1, world,
+                              is_master=(rank == 0))
     ids = frame_list(a.frames)
     if a.stand_in:
         pipe = StandInPipeline()
@@ -140,7 +157,8 @@ def main(argv=None):
         pipe.run_group([load(9, 1 + i) for i in range(a.group)])          # warm-up group: allocator, library autotuning, graph captures
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res = shard.run_sharded(ids, load, pipe, group_size=a.group, dataset_name=a.dataset, device=dev, fixed_time=a.fixed_time)
+    res = shard.run_sharded(ids, load, pipe, group_size=a.group, dataset_name=a.dataset, device=dev, fixed_time=a.fixed_time,
+                            prefetch=not a.no_prefetch, assignment=a.assign, store=store)
     if world > 1:
         dist.barrier()
     wall = time.perf_counter() - t0
@@ -156,6 +174,7 @@ def main(argv=None):
                               per_rank_busy_s=[round(x, 4) for x in busy],
                               per_rank_frames=[int(x) for x in res["stats"][:, 1]],
                               per_rank_instances=[int(x) for x in res["stats"][:, 2]], stand_in=bool(a.stand_in),
+                              assign=a.assign, prefetch=not a.no_prefetch,
                               scaling="unmeasured on hardware" if a.stand_in or world == 1 else "measured")))
     if world > 1:
         dist.destroy_process_group()
