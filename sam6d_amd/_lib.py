@@ -7,6 +7,7 @@ load, importing any op raises.
 import ctypes
 import glob
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -105,17 +106,14 @@ def lib():
         import torch  # noqa: F401  (must precede the CDLL)
 
         if not os.path.exists(SO_PATH):
-            raise RuntimeError(
-                f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(the HIP extension is mandatory; there is no fallback path)")
+            raise RuntimeError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(the HIP extension is mandatory; there is no fallback path)")
         L = ctypes.CDLL(SO_PATH)
-        L.s6d_strerror.restype = ctypes.c_char_p
-        L.s6d_strerror.argtypes = [ctypes.c_int]
-        L.s6d_last_hip_error.restype = ctypes.c_char_p
-        L.s6d_version.restype = ctypes.c_int
-        want = abi_version()
-        if L.s6d_version() != want:
-            raise RuntimeError(f"{SO_PATH} is ABI version {L.s6d_version()}, include/sam6d_hip.h is {want}: rebuild "
+        for name in prototypes():
+            if hasattr(L, name):
+                bind(L, name)
+        if L.s6d_version() != abi_version():
+            raise RuntimeError(f"{SO_PATH} is ABI version {L.s6d_version()}, include/sam6d_hip.h is {abi_version()}: rebuild "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
         _lib = L
     return _lib
@@ -131,17 +129,52 @@ def check(code, what):
         raise S6DError(f"{what}: {L.s6d_strerror(code).decode()} [{L.s6d_last_hip_error().decode()}]")
 
 
+# ------------------------------------------------------------------ the C ABI, read from its header
+_RESTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "const char *": ctypes.c_char_p}
+_ARGTYPES = {"*": ctypes.c_void_p, "int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def parse_header(text):
+    """Header text -> (S6D_ABI_VERSION, {name: (restype, (argtype, ...))}).  With the comments out every declaration there is
+    `int | long | const char * s6d_name(parameters);`, a parameter a pointer or a scalar; a type outside the two tables is an error
+    naming the prototype, never a skip.  A pointer is a c_void_p: None (NULL), an int (data_ptr()), a c_void_p or a ctypes array."""
+    version = int(re.search(r"#define\s+S6D_ABI_VERSION\s+(\d+)", text).group(1))
+    src = re.sub(r'/\*.*?\*/|//[^\n]*|^\s*#[^\n]*|extern\s+"C"\s*\{', "", text, flags=re.S | re.M)
+    protos = {}
+    for stmt in (" ".join(x.replace("*", " * ").split()) for x in src.split(";") if "s6d_" in x):
+        m = re.fullmatch(r"(.*?) ?\b(s6d_\w+) ?\((.*)\)", stmt)
+        params = [] if m is None or m.group(3).strip() in ("", "void") else [p.replace("const ", "").split() for p in m.group(3).split(",")]
+        kinds = ["*" if "*" in w or "[" in w[-1] else " ".join(w[:-1] or w) for w in params]              # `long lda` -> long; an unnamed `long` too
+        if m is None or m.group(1) not in _RESTYPES or any(k not in _ARGTYPES for k in kinds):
+            raise ValueError(f"sam6d_hip.h: cannot bind `{stmt}`: return types are {sorted(_RESTYPES)}, parameters pointers or {sorted(_ARGTYPES)[1:]}")
+        protos[m.group(2)] = (_RESTYPES[m.group(1)], tuple(_ARGTYPES[k] for k in kinds))
+    return version, protos
+
+
+with open(os.path.join(_HERE, "..", "include", "sam6d_hip.h")) as _f:
+    _ABI_VERSION, _PROTOTYPES = parse_header(_f.read())          # the one read of the header
+
+
 def abi_version():
     """S6D_ABI_VERSION of include/sam6d_hip.h."""
-    import re
+    return _ABI_VERSION
 
-    return int(re.search(r"#define\s+S6D_ABI_VERSION\s+(\d+)", open(os.path.join(_HERE, "..", "include", "sam6d_hip.h")).read()).group(1))
+
+def prototypes():
+    """{entry point: (restype, argtypes)} of every declaration in include/sam6d_hip.h."""
+    return _PROTOTYPES
 
 
 def declared_symbols():
     """Entry points declared in include/sam6d_hip.h (used by the export test)."""
-    import re
+    return sorted(prototypes())
 
-    hdr = open(os.path.join(_HERE, "..", "include", "sam6d_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(s6d_[a-z0-9_]+)\s*\(", hdr)))
+
+def bind(L, name):
+    """Entry point `name` of the loaded library L with the header's prototype attached.  lib() does this for the product library; a
+    library a test puts in its place (a host build of some kernels) is bound as ops._call meets a function whose argtypes is None."""
+    proto, fn = prototypes().get(name), getattr(L, name, None)
+    if proto is None or fn is None:
+        raise AttributeError(f"{name}: " + ("not declared in include/sam6d_hip.h" if proto is None else "not exported by the loaded library"))
+    fn.restype, fn.argtypes = proto
+    return fn

@@ -5,22 +5,23 @@ Every function enqueues hand-written gfx950 kernels on torch's current stream an
 returns freshly allocated outputs; none of them has a CPU implementation.
 """
 import ctypes
-import os
 
 import torch
 
 from . import _lib
 from . import policy
 
-_vp = ctypes.c_void_p
-
 
 def _stream():
-    return _vp(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _ptr(t):
-    return _vp(t.data_ptr())
+    return None if t is None else t.data_ptr()          # an optional operand that is left out (None) goes as NULL
+
+
+def _float3(values):
+    return (ctypes.c_float * 3)(*[float(v) for v in values])          # a host-side `const float[3]` operand (per-channel mean / std)
 
 
 def _chk(t, dtype, name, ndim=None):
@@ -35,10 +36,24 @@ def _chk(t, dtype, name, ndim=None):
         raise RuntimeError(f"{name} must have {ndim} dimensions")
 
 
+def _fn(fn_name, nargs):
+    """The entry point under the prototype include/sam6d_hip.h declares for it (attached once per function object: a library a test
+    puts in _lib._lib is bound as it is used).  ctypes then converts plain values and refuses what does not fit; it lets surplus
+    arguments through, so the count is checked here."""
+    fn = getattr(_lib.lib(), fn_name, None)
+    if fn is None or fn.argtypes is None:
+        fn = _lib.bind(_lib.lib(), fn_name)
+    if nargs != len(fn.argtypes):
+        raise TypeError(f"{fn_name} takes {len(fn.argtypes)} arguments ({nargs} given)")
+    return fn
+
+
 def _call(fn_name, *args):
-    fn = getattr(_lib.lib(), fn_name)
-    fn.restype = ctypes.c_int
-    _lib.check(fn(*args), fn_name)
+    _lib.check(_fn(fn_name, len(args))(*args), fn_name)
+
+
+def _size(fn_name, *args):
+    return _fn(fn_name, len(args))(*args)          # the `long s6d_*_workspace_bytes / _floats / _scratch_bytes` functions
 
 
 # ------------------------------------------------------------------ PointNet++ ops
@@ -48,8 +63,7 @@ def furthest_point_sampling(points, nsamples):
     B, N, _ = points.shape
     out = torch.empty(B, nsamples, dtype=torch.int32, device=points.device)
     tmp = torch.empty(B, N, dtype=torch.float32, device=points.device) if N > 4096 else None
-    _call("s6d_fps_f32", _ptr(points), B, N, int(nsamples), _ptr(tmp) if tmp is not None else _vp(0), _ptr(out),
-          _stream())
+    _call("s6d_fps_f32", _ptr(points), B, N, nsamples, _ptr(tmp), _ptr(out), _stream())
     return out
 
 
@@ -82,8 +96,7 @@ def ball_query(new_xyz, xyz, radius, nsample):
     B, M, _ = new_xyz.shape
     N = xyz.shape[1]
     out = torch.empty(B, M, int(nsample), dtype=torch.int32, device=xyz.device)
-    _call("s6d_ball_query_f32", _ptr(new_xyz), _ptr(xyz), B, N, M, ctypes.c_float(radius), int(nsample), _ptr(out),
-          _stream())
+    _call("s6d_ball_query_f32", _ptr(new_xyz), _ptr(xyz), B, N, M, radius, int(nsample), _ptr(out), _stream())
     return out
 
 
@@ -118,8 +131,7 @@ def weighted_procrustes(src, ref, weights, weight_thresh=0.0, eps=1e-5):
         raise ValueError(f"weighted_procrustes: src {tuple(src.shape)}, ref {tuple(ref.shape)}, weights {tuple(weights.shape)}")
     R = torch.empty(B, 3, 3, dtype=torch.float32, device=src.device)
     t = torch.empty(B, 3, dtype=torch.float32, device=src.device)
-    _call("s6d_weighted_procrustes_f32", _ptr(src), _ptr(ref), _ptr(weights), B, N, ctypes.c_float(weight_thresh), ctypes.c_float(eps), _ptr(R), _ptr(t),
-          _stream())
+    _call("s6d_weighted_procrustes_f32", _ptr(src), _ptr(ref), _ptr(weights), B, N, weight_thresh, eps, _ptr(R), _ptr(t), _stream())
     return R, t
 
 
@@ -134,8 +146,7 @@ def pose_hypotheses(pts1, pts2, pair):
     R = torch.empty(B, n, 3, 3, dtype=torch.float32, device=pts1.device)
     t = torch.empty(B, n, 3, dtype=torch.float32, device=pts1.device)
     dis = torch.empty(B, n, dtype=torch.float32, device=pts1.device)
-    _call("s6d_pose_hypotheses_f32", _ptr(pts1), _ptr(pts2), _ptr(pair), B, N1, N2, n, _ptr(R), _ptr(t), _ptr(dis),
-          _stream())
+    _call("s6d_pose_hypotheses_f32", _ptr(pts1), _ptr(pts2), _ptr(pair), B, N1, N2, n, _ptr(R), _ptr(t), _ptr(dis), _stream())
     return R, t, dis
 
 
@@ -146,7 +157,7 @@ def coarse_sample(atten, rand_u):
     B, M1, M2 = atten.shape
     pair = torch.empty(B, rand_u.shape[1], dtype=torch.int32, device=atten.device)
     w1 = torch.empty(B, M1 - 1, dtype=torch.float32, device=atten.device)
-    _call("s6d_coarse_sample_f32", _ptr(atten), _ptr(rand_u), B, M1, M2, int(rand_u.shape[1]), _ptr(pair), _ptr(w1), _stream())
+    _call("s6d_coarse_sample_f32", _ptr(atten), _ptr(rand_u), B, M1, M2, rand_u.shape[1], _ptr(pair), _ptr(w1), _stream())
     return pair, w1
 
 
@@ -159,7 +170,7 @@ def smallest_k(dis, Rs, ts, k):
     Rk = torch.empty(B, k, 3, 3, dtype=torch.float32, device=dis.device)
     tk = torch.empty(B, k, 3, dtype=torch.float32, device=dis.device)
     idx = torch.empty(B, k, dtype=torch.int32, device=dis.device)
-    _call("s6d_smallest_k_f32", _ptr(dis), _ptr(Rs), _ptr(ts), B, n, int(k), _ptr(Rk), _ptr(tk), _ptr(idx), _stream())
+    _call("s6d_smallest_k_f32", _ptr(dis), _ptr(Rs), _ptr(ts), B, n, k, _ptr(Rk), _ptr(tk), _ptr(idx), _stream())
     return Rk, tk, idx
 
 
@@ -209,8 +220,8 @@ def rpe_attention(q, k, v, qt, qb, embed, scale):
     _chk(embed, embed.dtype if embed.dtype == torch.float16 else torch.float32, "embed", 4)
     B, N, C = q.shape
     out = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
-    _call("s6d_rpe_attention_strided_e16_f32" if embed.dtype == torch.float16 else "s6d_rpe_attention_strided_f32", _ptr(q), ctypes.c_long(ldq), _ptr(k), ctypes.c_long(ldk), _ptr(v), ctypes.c_long(ldv),
-          _ptr(qt), _ptr(qb), _ptr(embed), B, N, C, 4, ctypes.c_float(scale), _ptr(out), _stream())
+    _call("s6d_rpe_attention_strided_e16_f32" if embed.dtype == torch.float16 else "s6d_rpe_attention_strided_f32", _ptr(q), ldq, _ptr(k),
+          ldk, _ptr(v), ldv, _ptr(qt), _ptr(qb), _ptr(embed), B, N, C, 4, scale, _ptr(out), _stream())
     return out
 
 
@@ -221,8 +232,8 @@ def rpe_attention_packed(proj, embed, scale, q_off=0, k_off=256, v_off=512, qt_o
     _chk(embed, embed.dtype if embed.dtype == torch.float16 else torch.float32, "embed", 4)
     B, N, ld = proj.shape
     out = torch.empty(B, N, 256, dtype=torch.float32, device=proj.device)
-    _call("s6d_rpe_attention_packed_e16_f32" if embed.dtype == torch.float16 else "s6d_rpe_attention_packed_f32", _ptr(proj), ctypes.c_long(ld), int(q_off), int(k_off), int(v_off), int(qt_off), int(qb_off),
-          _ptr(embed), B, N, 256, 4, ctypes.c_float(scale), _ptr(out), _stream())
+    _call("s6d_rpe_attention_packed_e16_f32" if embed.dtype == torch.float16 else "s6d_rpe_attention_packed_f32", _ptr(proj), ld,
+          int(q_off), int(k_off), int(v_off), int(qt_off), int(qb_off), _ptr(embed), B, N, 256, 4, scale, _ptr(out), _stream())
     return out
 
 
@@ -234,9 +245,7 @@ def sam_preprocess(x, mean, std, img_size, out_dtype=torch.bfloat16):
     if C != 3:
         raise RuntimeError("x must have 3 channels")
     out = torch.empty(B, 3, img_size, img_size, dtype=out_dtype, device=x.device)
-    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
-    s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    _call("s6d_sam_preprocess_f32", _ptr(x), B, h, w, int(img_size), m, s, 1 if out_dtype == torch.bfloat16 else 0,
+    _call("s6d_sam_preprocess_f32", _ptr(x), B, h, w, int(img_size), _float3(mean), _float3(std), 1 if out_dtype == torch.bfloat16 else 0,
           _ptr(out), _stream())
     return out
 
@@ -247,7 +256,7 @@ def nonfinite_rows(x):
     B = x.shape[0]
     n = x.numel() // max(B, 1)
     flags = torch.empty(B, dtype=torch.int32, device=x.device)
-    _call("s6d_nonfinite_rows_f32", _ptr(x), B, ctypes.c_long(n), _ptr(flags), _stream())
+    _call("s6d_nonfinite_rows_f32", _ptr(x), B, n, _ptr(flags), _stream())
     return flags.bool()
 
 
@@ -289,10 +298,8 @@ def crop_resize_pad(image_u8, masks, params, target, mean, std, rgb=True, mask=T
     T = int(target)
     o_rgb = torch.empty(P, 3, T, T, dtype=torch.float32, device=masks.device) if rgb else None
     o_mask = torch.empty(P, T, T, dtype=torch.float32, device=masks.device) if mask else None
-    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
-    sd = (ctypes.c_float * 3)(*[float(v) for v in std])
-    _call("s6d_crop_resize_pad_f32", _ptr(image_u8) if rgb else _vp(0), _ptr(masks), _ptr(params), P, H, W, T, m, sd,
-          _ptr(o_rgb) if rgb else _vp(0), _ptr(o_mask) if mask else _vp(0), _stream())
+    _call("s6d_crop_resize_pad_f32", _ptr(image_u8) if rgb else None, _ptr(masks), _ptr(params), P, H, W, T, _float3(mean), _float3(std),
+          _ptr(o_rgb), _ptr(o_mask), _stream())
     return o_rgb, o_mask
 
 
@@ -315,9 +322,8 @@ def samdec_img2tok(q, q_add, kexp, vpt, resid, out_bias, ln_w, ln_b, eps, n_tok)
     if tuple(kexp.shape) != (B, 64, 128) or tuple(vpt.shape) != (B, 256, 64) or resid.shape[2] != 256 or q.shape[1] != N:
         raise RuntimeError("samdec_img2tok: shape mismatch")
     out = torch.empty(B, N, 256, dtype=torch.bfloat16, device=kexp.device)
-    _call("s6d_samdec_img2tok_bf16", _ptr(q), _ptr(q_add) if q_add is not None else _vp(0), _ptr(kexp), _ptr(vpt),
-          _ptr(resid), _ptr(out_bias), _ptr(ln_w), _ptr(ln_b), ctypes.c_float(eps), B, N, int(n_tok), int(q_ld),
-          1 if q.shape[0] == 1 and B > 1 else 0, 1 if resid.shape[0] == 1 and B > 1 else 0, _ptr(out), _stream())
+    _call("s6d_samdec_img2tok_bf16", _ptr(q), _ptr(q_add), _ptr(kexp), _ptr(vpt), _ptr(resid), _ptr(out_bias), _ptr(ln_w), _ptr(ln_b), eps,
+          B, N, int(n_tok), q_ld, 1 if q.shape[0] == 1 and B > 1 else 0, 1 if resid.shape[0] == 1 and B > 1 else 0, _ptr(out), _stream())
     return out
 
 
@@ -337,9 +343,9 @@ def samdec_img2tok_raw(x, pe, kexp256, cbias, vpt, resid, out_bias, ln_w, ln_b, 
             or tuple(cbias.shape) != (B, 64) or x.shape[0] not in (1, B) or resid.shape[0] not in (1, B)):
         raise RuntimeError("samdec_img2tok_raw: shape mismatch")
     out = torch.empty(B, N, 256, dtype=torch.bfloat16, device=kexp256.device)
-    _call("s6d_samdec_img2tok_raw_bf16", _ptr(x), _ptr(pe) if pe is not None else _vp(0), _ptr(kexp256), _ptr(cbias), _ptr(vpt),
-          _ptr(resid), _ptr(out_bias), _ptr(ln_w), _ptr(ln_b), ctypes.c_float(eps), B, N, int(n_tok), 256,
-          1 if x.shape[0] == 1 and B > 1 else 0, 1 if resid.shape[0] == 1 and B > 1 else 0, _ptr(out), _stream())
+    _call("s6d_samdec_img2tok_raw_bf16", _ptr(x), _ptr(pe), _ptr(kexp256), _ptr(cbias), _ptr(vpt), _ptr(resid), _ptr(out_bias), _ptr(ln_w),
+          _ptr(ln_b), eps, B, N, int(n_tok), 256, 1 if x.shape[0] == 1 and B > 1 else 0, 1 if resid.shape[0] == 1 and B > 1 else 0,
+          _ptr(out), _stream())
     return out
 
 
@@ -355,9 +361,8 @@ def samdec_tok2img(qt, kv, k_off, v_off, k_pe, scale):
     if k_pe is not None:
         _chk(k_pe, torch.bfloat16, "k_pe", 2)
     out = torch.empty(B, 8, 128, dtype=torch.float32, device=qt.device)
-    _call("s6d_samdec_tok2img_f32", _ptr(q8), _ptr(kv), int(kv.shape[2]), int(k_off), int(v_off),
-          1 if kv.shape[0] == 1 and B > 1 else 0, _ptr(k_pe) if k_pe is not None else _vp(0), B, int(kv.shape[1]),
-          ctypes.c_float(scale), _ptr(out), _stream())
+    _call("s6d_samdec_tok2img_f32", _ptr(q8), _ptr(kv), kv.shape[2], int(k_off), int(v_off), 1 if kv.shape[0] == 1 and B > 1 else 0,
+          _ptr(k_pe), B, kv.shape[1], scale, _ptr(out), _stream())
     return out[:, :T]
 
 
@@ -378,9 +383,7 @@ def samdec_tok2img_raw(qt, x, pe, wk, wv, bv, scale):
         qp = torch.zeros(B, H, 8, 256, dtype=torch.float32, device=qt.device)
         qp[:, :, :T] = torch.einsum("bthd,hdc->bhtc", qt.view(B, T, H, hd) * (scale * 1.4426950408889634), wk.float().view(H, hd, 256))
         qp = qp.to(torch.bfloat16).view(B, 64, 256)
-        y = torch.empty(B, 64, 256, dtype=torch.float32, device=qt.device)
-        _call("s6d_samdec_tok2img_raw_bf16", _ptr(qp), _ptr(x), int(x.stride(1)), 1 if x.shape[0] == 1 and B > 1 else 0,
-              _ptr(pe) if pe is not None else _vp(0), B, int(x.shape[1]), _ptr(y), _stream())
+        y = samdec_tok2img_raw_core(qp, x, pe)
         out = torch.einsum("bhtc,hdc->bthd", y.view(B, H, 8, 256)[:, :, :T], wv.float().view(H, hd, 256)) + bv.float().view(1, 1, H, hd)
     return out.reshape(B, T, 128)
 
@@ -400,13 +403,13 @@ def samdec_tokens_pre(queries, pe, add_pe, lin_q, lin_k, lin_v, lin_o, norm1, li
     q1 = torch.empty(B, T, 256, dtype=torch.float32, device=queries.device)
     if fold is None:
         out2 = torch.empty(B, T, 128, dtype=torch.float32, device=queries.device)
-        qp_ptr, wk_ptr, sc, qf_ptr = _ptr(out2), _vp(0), 0.0, _vp(0)
+        qp_ptr, wk_ptr, sc, qf_ptr = _ptr(out2), None, 0.0, None
     else:
         out2 = torch.empty(B, 64, 256, dtype=torch.bfloat16, device=queries.device)
-        qp_ptr, wk_ptr, sc, qf_ptr = _vp(0), _ptr(fold[0]), float(fold[1]), _ptr(out2)
+        qp_ptr, wk_ptr, sc, qf_ptr = None, _ptr(fold[0]), float(fold[1]), _ptr(out2)
     _call("s6d_samdec_tokens_pre_bf16", _ptr(queries), _ptr(pe), B, T, 1 if add_pe else 0, _ptr(lin_q[0]), _ptr(lin_q[1]), _ptr(lin_k[0]),
-          _ptr(lin_k[1]), _ptr(lin_v[0]), _ptr(lin_v[1]), _ptr(lin_o[0]), _ptr(lin_o[1]), _ptr(norm1[0]), _ptr(norm1[1]),
-          ctypes.c_float(norm1[2]), _ptr(lin_q2[0]), _ptr(lin_q2[1]), _ptr(q1), qp_ptr, wk_ptr, ctypes.c_float(sc), qf_ptr, _stream())
+          _ptr(lin_k[1]), _ptr(lin_v[0]), _ptr(lin_v[1]), _ptr(lin_o[0]), _ptr(lin_o[1]), _ptr(norm1[0]), _ptr(norm1[1]), norm1[2],
+          _ptr(lin_q2[0]), _ptr(lin_q2[1]), _ptr(q1), qp_ptr, wk_ptr, sc, qf_ptr, _stream())
     return q1, out2
 
 
@@ -421,8 +424,8 @@ def samdec_tok2img_raw_core(qfold, x, pe):
     if pe is not None:
         _chk(pe, torch.bfloat16, "pe", 2)
     y = torch.empty(B, 64, 256, dtype=torch.float32, device=qfold.device)
-    _call("s6d_samdec_tok2img_raw_bf16", _ptr(qfold), _ptr(x), int(x.stride(1)), 1 if x.shape[0] == 1 and B > 1 else 0,
-          _ptr(pe) if pe is not None else _vp(0), B, int(x.shape[1]), _ptr(y), _stream())
+    _call("s6d_samdec_tok2img_raw_bf16", _ptr(qfold), _ptr(x), x.stride(1), 1 if x.shape[0] == 1 and B > 1 else 0, _ptr(pe), B, x.shape[1],
+          _ptr(y), _stream())
     return y
 
 
@@ -449,29 +452,28 @@ def samdec_tokens_post(q1, att, pe, lin_o2, norm2, lin_1, lin_2, norm3, lin_k3, 
     q1, pe = q1.contiguous(), pe.contiguous()
     dev = q1.device
     q3 = torch.empty(B, T, 256, dtype=torch.float32, device=dev)
-    null = _vp(0)
     if expand is None:
         kt = torch.empty(B, T, 128, dtype=torch.float32, device=dev)
         vt = torch.empty(B, T, 128, dtype=torch.float32, device=dev)
         tail = (_ptr(kt), _ptr(vt))
-        ex = (null, null, null, null, null, null, null)
+        ex = (None,) * 7
         res = (q3, kt, vt)
     else:
         out = {"vpt": torch.empty(B, 256, 64, dtype=torch.bfloat16, device=dev)}
         if expand["fold_q"]:
             out["k256"] = torch.empty(B, 64, 256, dtype=torch.bfloat16, device=dev)
             out["cb"] = torch.empty(B, 64, dtype=torch.float32, device=dev)
-            ex = (_ptr(expand["wq"]), _ptr(expand["bq"]), _ptr(expand["wo"]), null, _ptr(out["k256"]), _ptr(out["cb"]), _ptr(out["vpt"]))
+            ex = (_ptr(expand["wq"]), _ptr(expand["bq"]), _ptr(expand["wo"]), None, _ptr(out["k256"]), _ptr(out["cb"]), _ptr(out["vpt"]))
         else:
             out["kexp"] = torch.zeros(B, 64, 128, dtype=torch.bfloat16, device=dev)      # block diagonal: the kernel writes the blocks
-            ex = (null, null, _ptr(expand["wo"]), _ptr(out["kexp"]), null, null, _ptr(out["vpt"]))
-        tail = (null, null)
+            ex = (None, None, _ptr(expand["wo"]), _ptr(out["kexp"]), None, None, _ptr(out["vpt"]))
+        tail = (None, None)
         res = (q3, out)
-    yargs = (null, null, null) if y is None else (_ptr(y), _ptr(vfold[0]), _ptr(vfold[1]))
-    _call("s6d_samdec_tokens_post_bf16", _ptr(q1), _ptr(att) if y is None else null, _ptr(pe), B, T, _ptr(lin_o2[0]), _ptr(lin_o2[1]),
-          _ptr(norm2[0]), _ptr(norm2[1]), ctypes.c_float(norm2[2]), _ptr(lin_1[0]), _ptr(lin_1[1]), _ptr(lin_2[0]), _ptr(lin_2[1]),
-          _ptr(norm3[0]), _ptr(norm3[1]), ctypes.c_float(norm3[2]), _ptr(lin_k3[0]), _ptr(lin_k3[1]), _ptr(lin_v3[0]), _ptr(lin_v3[1]),
-          _ptr(q3), *tail, *yargs, *ex, _stream())
+    yargs = (None,) * 3 if y is None else (_ptr(y), _ptr(vfold[0]), _ptr(vfold[1]))
+    _call("s6d_samdec_tokens_post_bf16", _ptr(q1), _ptr(att) if y is None else None, _ptr(pe), B, T, _ptr(lin_o2[0]), _ptr(lin_o2[1]),
+          _ptr(norm2[0]), _ptr(norm2[1]), norm2[2], _ptr(lin_1[0]), _ptr(lin_1[1]), _ptr(lin_2[0]), _ptr(lin_2[1]), _ptr(norm3[0]),
+          _ptr(norm3[1]), norm3[2], _ptr(lin_k3[0]), _ptr(lin_k3[1]), _ptr(lin_v3[0]), _ptr(lin_v3[1]), _ptr(q3), *tail, *yargs, *ex,
+          _stream())
     return res
 
 
@@ -497,9 +499,8 @@ def sam_mask_post(low_res, img_size, input_size, original_size, mask_threshold=0
     masks = torch.empty(Bm, H, W, dtype=torch.bool, device=low_res.device)      # the kernel writes 0 / 1 bytes: no uint8 -> bool pass
     stats = torch.empty(Bm, 6, dtype=torch.int32, device=low_res.device)
     # the slice's data pointer is its first plane: mask (b, c) reads plane b * ct + c from there
-    _call("s6d_sam_mask_post_sel_f32", _ptr(low_res), int(B), int(ct), 0, int(max(C, 1)), int(n), int(img_size), int(input_size[0]),
-          int(input_size[1]), int(H), int(W), ctypes.c_float(mask_threshold), ctypes.c_float(stability_offset), _ptr(masks),
-          _ptr(stats), _stream())
+    _call("s6d_sam_mask_post_sel_f32", _ptr(low_res), B, ct, 0, max(C, 1), n, int(img_size), int(input_size[0]), int(input_size[1]), H, W,
+          mask_threshold, stability_offset, _ptr(masks), _ptr(stats), _stream())
     stability = stats[:, 0] / stats[:, 1]                           # int32 / int32 -> float32, NaN for 0 / 0 like the reference
     empty = (stats[:, 4] < stats[:, 2]) | (stats[:, 5] < stats[:, 3])
     boxes = stats[:, 2:6].long() * (~empty).unsqueeze(-1)
@@ -513,11 +514,9 @@ def nms(boxes, scores, iou_threshold):
     if N == 0:
         return torch.empty(0, dtype=torch.int64, device=boxes.device)
     order = torch.sort(scores.float(), descending=True, stable=True)[1].contiguous()
-    fn = _lib.lib().s6d_nms_workspace_bytes
-    fn.restype = ctypes.c_long
-    ws = torch.empty(max(int(fn(N)), 8), dtype=torch.uint8, device=boxes.device)
+    ws = torch.empty(max(_size("s6d_nms_workspace_bytes", N), 8), dtype=torch.uint8, device=boxes.device)
     keep = torch.empty(N, dtype=torch.uint8, device=boxes.device)
-    _call("s6d_nms_f32", _ptr(boxes), _ptr(order), N, ctypes.c_float(iou_threshold), _ptr(ws), _ptr(keep), _stream())
+    _call("s6d_nms_f32", _ptr(boxes), _ptr(order), N, iou_threshold, _ptr(ws), _ptr(keep), _stream())
     return order[keep.bool()]
 
 
@@ -538,8 +537,8 @@ def samdec_upscale_heads(y0, ln_w, ln_b, eps, w2t, b2, hyper, h, w):
     if N != h * w or tuple(w2t.shape) != (128, 64) or hyper.shape[2] != 32 or hyper.shape[0] != B:
         raise RuntimeError("samdec_upscale_heads: shape mismatch")
     masks = torch.empty(B, M, 4 * h, 4 * w, dtype=torch.float32, device=y0.device)
-    _call("s6d_samdec_upscale_heads_bf16", _ptr(y0), _ptr(ln_w), _ptr(ln_b), ctypes.c_float(eps), _ptr(w2t), _ptr(b2),
-          _ptr(hyper), B, M, int(h), int(w), int(y_ld), _ptr(masks), _stream())
+    _call("s6d_samdec_upscale_heads_bf16", _ptr(y0), _ptr(ln_w), _ptr(ln_b), eps, _ptr(w2t), _ptr(b2), _ptr(hyper), B, M, h, w, y_ld,
+          _ptr(masks), _stream())
     return masks
 
 
@@ -567,8 +566,7 @@ def pem_sample_indices(keys, count, n_sample):
         raise RuntimeError("pem_sample_indices: one count per row of keys")
     idx = torch.zeros(P, n_sample, dtype=torch.int64, device=keys.device)
     overflow = torch.zeros(P, dtype=torch.int32, device=keys.device)
-    _call("s6d_pem_sample_indices_f32", _ptr(keys), ctypes.c_long(L), _ptr(count), P, int(n_sample), _ptr(idx), _ptr(overflow),
-          _stream())
+    _call("s6d_pem_sample_indices_f32", _ptr(keys), L, _ptr(count), P, n_sample, _ptr(idx), _ptr(overflow), _stream())
     return idx, overflow
 
 
@@ -585,8 +583,7 @@ def pem_mask_boxes(mask8, depth, min_points):
     cnt = torch.zeros(P, dtype=torch.int64, device=dev)
     ok8 = torch.zeros(P, dtype=torch.uint8, device=dev)
     box = torch.zeros(P, 4, dtype=torch.int64, device=dev)
-    _call("s6d_pem_mask_boxes_u8", _ptr(mask8), _ptr(depth), P, H, W, ctypes.c_long(int(min_points)), _ptr(m8), _ptr(cnt), _ptr(ok8),
-          _ptr(box), _stream())
+    _call("s6d_pem_mask_boxes_u8", _ptr(mask8), _ptr(depth), P, H, W, int(min_points), _ptr(m8), _ptr(cnt), _ptr(ok8), _ptr(box), _stream())
     return m8, cnt, ok8, box
 
 
@@ -601,8 +598,8 @@ def pem_crops(image_u8, m8, kept, box, S, use_mask, mean, std):
         raise RuntimeError("pem_crops: shape mismatch")
     M = kept.shape[0]
     out = torch.empty(M, 3, S, S, dtype=torch.float32, device=m8.device)
-    _call("s6d_pem_crops_f32", _ptr(image_u8), _ptr(m8), _ptr(kept), _ptr(box), M, H, W, int(S), int(bool(use_mask)),
-          (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), _ptr(out), _stream())
+    _call("s6d_pem_crops_f32", _ptr(image_u8), _ptr(m8), _ptr(kept), _ptr(box), M, H, W, S, bool(use_mask), _float3(mean), _float3(std),
+          _ptr(out), _stream())
     return out
 
 
@@ -619,8 +616,8 @@ def pem_compact_cloud(m8, depth, box, ok8, fx, fy, cx, cy, cap):
     choose = torch.empty(P, cap, dtype=torch.int32, device=m8.device)
     cloud = torch.empty(P, cap, 3, dtype=torch.float32, device=m8.device)
     n = torch.zeros(P, dtype=torch.int64, device=m8.device)
-    _call("s6d_pem_compact_cloud_f32", _ptr(m8), _ptr(depth), _ptr(box), _ptr(ok8), P, H, W, ctypes.c_float(fx), ctypes.c_float(fy),
-          ctypes.c_float(cx), ctypes.c_float(cy), ctypes.c_long(cap), _ptr(choose), _ptr(cloud), _ptr(n), _stream())
+    _call("s6d_pem_compact_cloud_f32", _ptr(m8), _ptr(depth), _ptr(box), _ptr(ok8), P, H, W, fx, fy, cx, cy, cap, _ptr(choose), _ptr(cloud),
+          _ptr(n), _stream())
     return choose, cloud, n
 
 
@@ -634,7 +631,7 @@ def pem_radius_filter(center, limit, choose, cloud, n):
     P, cap = choose.shape
     if tuple(center.shape) != (P, 3) or limit.shape[0] != P or tuple(cloud.shape) != (P, cap, 3) or n.shape[0] != P:
         raise RuntimeError("pem_radius_filter: shape mismatch")
-    _call("s6d_pem_radius_filter_f32", _ptr(center), _ptr(limit), P, ctypes.c_long(cap), _ptr(choose), _ptr(cloud), _ptr(n), _stream())
+    _call("s6d_pem_radius_filter_f32", _ptr(center), _ptr(limit), P, cap, _ptr(choose), _ptr(cloud), _ptr(n), _stream())
     return n
 
 
@@ -647,7 +644,7 @@ def upsample_gather(up, choose, H, W, C):
     P = int(round((PC // C) ** 0.5))
     n = choose.shape[1]
     out = torch.empty(B, n, C, dtype=torch.float32, device=up.device)
-    _call("s6d_upsample_gather_f32", _ptr(up), _ptr(choose), B, n, G, P, int(C), int(H), int(W), _ptr(out), _stream())
+    _call("s6d_upsample_gather_f32", _ptr(up), _ptr(choose), B, n, G, P, C, int(H), int(W), _ptr(out), _stream())
     return out
 
 
@@ -661,9 +658,7 @@ def _padded_rel(rel_h, rel_w, H, window, hd):
     key = (id(rel_h), id(rel_w), H, window, hd)
     c = _REL_PAD.get(key)
     if c is None or c[0] is not rel_h or c[1] is not rel_w or c[2] != (rel_h._version, rel_w._version):
-        fn = _lib.lib().s6d_win_attention_scratch_bytes
-        fn.restype = ctypes.c_long
-        pad = torch.empty(int(fn(H, window, hd)), dtype=torch.uint8, device=rel_h.device)
+        pad = torch.empty(_size("s6d_win_attention_scratch_bytes", H, window, hd), dtype=torch.uint8, device=rel_h.device)
         _call("s6d_win_attention_pad_rel_bf16", _ptr(rel_h), _ptr(rel_w), H, window, hd, _ptr(pad), _stream())
         if len(_REL_PAD) > 256:
             _REL_PAD.clear()
@@ -699,11 +694,11 @@ def window_attention(qkv, qkv_bias, rel_h, rel_w, num_heads, window, scale, head
         # the padded copies of the two tables the kernels read are a function of the tables only: made once per (table pair, grid,
         # window) and kept (round 6: the padding ran as a 5-us launch in front of each of the 64 attention launches of a step)
         _call("s6d_win_attention_prepadded_bf16", _ptr(qkv), 0 if head_major_shape is None else 1, _ptr(qkv_bias),
-              _ptr(_padded_rel(rel_h, rel_w, H, int(window), int(hd))), B, H, W, int(num_heads), int(hd), int(window), ctypes.c_float(scale),
-              _ptr(out), _stream())
+              _ptr(_padded_rel(rel_h, rel_w, H, int(window), int(hd))), B, H, W, int(num_heads), int(hd), int(window), scale, _ptr(out),
+              _stream())
         return out
-    _call("s6d_win_attention_layout_bf16", _ptr(qkv), 0 if head_major_shape is None else 1, _ptr(qkv_bias), _vp(0), _vp(0), B, H, W,
-          int(num_heads), int(hd), int(window), ctypes.c_float(scale), _vp(0), _ptr(out), _stream())
+    _call("s6d_win_attention_layout_bf16", _ptr(qkv), 0 if head_major_shape is None else 1, _ptr(qkv_bias), None, None, B, H, W,
+          int(num_heads), int(hd), int(window), scale, None, _ptr(out), _stream())
     return out
 
 
@@ -725,8 +720,7 @@ def seq_attention(qkv, num_heads, scale, seq_len=None):
         B, N, C3 = qkv.shape
         C = C3 // 3
         out = torch.empty(B, N, C, dtype=qkv.dtype, device=qkv.device)
-        _call("s6d_seq_attention_" + sfx, _ptr(qkv), B, N, int(num_heads), int(C // num_heads), ctypes.c_float(scale),
-              _ptr(out), _stream())
+        _call("s6d_seq_attention_" + sfx, _ptr(qkv), B, N, int(num_heads), int(C // num_heads), scale, _ptr(out), _stream())
         return out
     H3, M, hd = qkv.shape
     N = int(seq_len)
@@ -734,8 +728,8 @@ def seq_attention(qkv, num_heads, scale, seq_len=None):
         raise ValueError(f"head-major qkv must be (3 * num_heads, B * N, hd); got {tuple(qkv.shape)} for {num_heads} heads, N = {N}")
     B = M // N
     out = torch.empty(B, N, num_heads * hd, dtype=qkv.dtype, device=qkv.device)
-    _call("s6d_seq_attention_strided_" + sfx, _ptr(qkv), ctypes.c_long(hd), ctypes.c_long(num_heads * M * hd), ctypes.c_long(M * hd),
-          B, N, int(num_heads), int(hd), ctypes.c_float(scale), _ptr(out), _stream())
+    _call("s6d_seq_attention_strided_" + sfx, _ptr(qkv), hd, num_heads * M * hd, M * hd, B, N, int(num_heads), hd, scale, _ptr(out),
+          _stream())
     return out
 
 
@@ -767,9 +761,8 @@ def gemm_bf16(a, w, bias=None, gelu=False, out=None, max_blocks=0, col_block=0, 
         if out is not None:
             raise RuntimeError("col_block output is allocated by the call")
         out = torch.empty(N // col_block, M, col_block, dtype=torch.bfloat16, device=a.device)   # (bf16 only: checked above)
-        _call("s6d_gemm_bf16_cblk", _ptr(a2), ctypes.c_long(a2.stride(0)), _ptr(w), ctypes.c_long(w.stride(0)),
-              _ptr(bias) if bias is not None else _vp(0), _ptr(out), ctypes.c_long(N), M, N, K, 1 if gelu else 0, int(col_block),
-              int(max_blocks), _stream())
+        _call("s6d_gemm_bf16_cblk", _ptr(a2), a2.stride(0), _ptr(w), w.stride(0), _ptr(bias), _ptr(out), N, M, N, K, 1 if gelu else 0,
+              int(col_block), int(max_blocks), _stream())
         return out
     if out is None:
         out = torch.empty(M, N, dtype=a.dtype, device=a.device)
@@ -798,18 +791,15 @@ def gemm_bf16(a, w, bias=None, gelu=False, out=None, max_blocks=0, col_block=0, 
                 raise RuntimeError("row statistics are written for one launch: the row count exceeds one 2-GiB slab")
         for r0 in range(0, M, rows):
             r1 = min(M, r0 + rows)
-            _call("s6d_gemm_bf16_res", _ptr(a2[r0:r1]), ctypes.c_long(a2.stride(0)), _ptr(w), ctypes.c_long(w.stride(0)),
-                  _ptr(bias) if bias is not None else _vp(0), _ptr(r2[r0:r1]), ctypes.c_long(r2.stride(0)),
-                  _ptr(stats_partial) if stats_partial is not None else _vp(0), _ptr(out[r0:r1]),
-                  ctypes.c_long(out.stride(0)), r1 - r0, N, K, int(max_blocks), _stream())
+            _call("s6d_gemm_bf16_res", _ptr(a2[r0:r1]), a2.stride(0), _ptr(w), w.stride(0), _ptr(bias), _ptr(r2[r0:r1]), r2.stride(0),
+                  _ptr(stats_partial), _ptr(out[r0:r1]), out.stride(0), r1 - r0, N, K, int(max_blocks), _stream())
         return out.reshape(*a.shape[:-1], N)
     if stats_partial is not None:
         raise RuntimeError("stats_partial comes with the residual form")
     for r0 in range(0, M, rows):
         r1 = min(M, r0 + rows)
-        _call("s6d_gemm_f16" if f16 else "s6d_gemm_bf16", _ptr(a2[r0:r1]), ctypes.c_long(a2.stride(0)), _ptr(w), ctypes.c_long(w.stride(0)),
-              _ptr(bias) if bias is not None else _vp(0), _ptr(out[r0:r1]), ctypes.c_long(out.stride(0)), r1 - r0, N, K,
-              1 if gelu else 0, int(max_blocks), _stream())
+        _call("s6d_gemm_f16" if f16 else "s6d_gemm_bf16", _ptr(a2[r0:r1]), a2.stride(0), _ptr(w), w.stride(0), _ptr(bias), _ptr(out[r0:r1]),
+              out.stride(0), r1 - r0, N, K, 1 if gelu else 0, int(max_blocks), _stream())
     return out.reshape(*a.shape[:-1], N)
 
 
@@ -846,7 +836,7 @@ def ln_stats_finalize(stats_partial, group_size=32, eps=1e-6):
         raise ValueError("stats_partial must be a contiguous (groups, 2, M) tensor")
     G, _, M = stats_partial.shape
     out = torch.empty(M, 2, dtype=torch.float32, device=stats_partial.device)
-    _call("s6d_ln_stats_finalize", _ptr(stats_partial), int(G), int(group_size), ctypes.c_long(M), ctypes.c_float(eps), _ptr(out), _stream())
+    _call("s6d_ln_stats_finalize", _ptr(stats_partial), G, int(group_size), M, eps, _ptr(out), _stream())
     return out
 
 
@@ -858,8 +848,7 @@ def row_stats(x, eps=1e-6):
     if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
         x2 = x2.contiguous()
     out = torch.empty(x2.shape[0], 2, dtype=torch.float32, device=x.device)
-    _call("s6d_row_stats_bf16", _ptr(x2), ctypes.c_long(x2.stride(0)), ctypes.c_long(x2.shape[0]), int(C), ctypes.c_float(eps), _ptr(out),
-          _stream())
+    _call("s6d_row_stats_bf16", _ptr(x2), x2.stride(0), x2.shape[0], C, eps, _ptr(out), _stream())
     return out
 
 
@@ -885,12 +874,10 @@ def gemm_bf16_lnfold(a, stats, w_folded, col_sums, bias, gelu=False, col_block=0
         raise RuntimeError("one launch: the row count exceeds one 2-GiB slab")
     if col_block:
         out = torch.empty(N // col_block, M, col_block, dtype=torch.bfloat16, device=a.device)
-        ldc = N
     else:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
-        ldc = N
-    _call("s6d_gemm_bf16_lnfold", _ptr(a2), ctypes.c_long(a2.stride(0)), _ptr(stats), _ptr(w_folded), ctypes.c_long(w_folded.stride(0)),
-          _ptr(col_sums), _ptr(bias), _ptr(out), ctypes.c_long(ldc), M, N, K, 1 if gelu else 0, int(col_block), int(max_blocks), _stream())
+    _call("s6d_gemm_bf16_lnfold", _ptr(a2), a2.stride(0), _ptr(stats), _ptr(w_folded), w_folded.stride(0), _ptr(col_sums), _ptr(bias),
+          _ptr(out), N, M, N, K, 1 if gelu else 0, int(col_block), int(max_blocks), _stream())
     return out if col_block else out.reshape(*a.shape[:-1], N)
 
 
@@ -911,9 +898,8 @@ def gemm_fp8(a8, a_scale, w8, w_scale, bias=None, gelu=False, max_blocks=0):
     rows = max(256, ((2 ** 31 - 1) // K) // 256 * 256)
     for r0 in range(0, M, rows):
         r1 = min(M, r0 + rows)
-        _call("s6d_gemm_fp8", _ptr(a2[r0:r1]), ctypes.c_long(K), _ptr(a_scale.reshape(-1)[r0:r1]), _ptr(w8), ctypes.c_long(K),
-              _ptr(w_scale), _ptr(bias) if bias is not None else _vp(0), _ptr(out[r0:r1]), ctypes.c_long(N), r1 - r0, N, K,
-              1 if gelu else 0, int(max_blocks), _stream())
+        _call("s6d_gemm_fp8", _ptr(a2[r0:r1]), K, _ptr(a_scale.reshape(-1)[r0:r1]), _ptr(w8), K, _ptr(w_scale), _ptr(bias),
+              _ptr(out[r0:r1]), N, r1 - r0, N, K, 1 if gelu else 0, int(max_blocks), _stream())
     return out.reshape(*a8.shape[:-1], N)
 
 
@@ -935,8 +921,8 @@ def gemm_fp8_gelu_mx(a8, a_scale, w8, w_scale, bias=None, max_blocks=0):
     q = torch.empty(M, N, dtype=torch.uint8, device=a8.device)
     Mp = (M + 255) // 256 * 256                 # the consumer fetches the scale dwords of whole 256-row tiles: the rows exist
     s = torch.zeros(Mp, N // 32, dtype=torch.uint8, device=a8.device)[:M]
-    _call("s6d_gemm_fp8_gelu_mx", _ptr(a2), ctypes.c_long(K), _ptr(a_scale.reshape(-1)), _ptr(w8), ctypes.c_long(K), _ptr(w_scale),
-          _ptr(bias) if bias is not None else _vp(0), _ptr(q), ctypes.c_long(N), _ptr(s), M, N, K, int(max_blocks), _stream())
+    _call("s6d_gemm_fp8_gelu_mx", _ptr(a2), K, _ptr(a_scale.reshape(-1)), _ptr(w8), K, _ptr(w_scale), _ptr(bias), _ptr(q), N, _ptr(s), M, N,
+          K, int(max_blocks), _stream())
     return q, s
 
 
@@ -960,8 +946,8 @@ def gemm_fp8_mxa(a8, a_mx, w8, w_scale, bias=None, gelu=False, max_blocks=0):
         pad[:M] = a_mx
         a_mx = pad[:M]
     out = torch.empty(M, N, dtype=torch.bfloat16, device=a8.device)
-    _call("s6d_gemm_fp8_mxa", _ptr(a2), ctypes.c_long(K), _ptr(a_mx), _ptr(w8), ctypes.c_long(K), _ptr(w_scale),
-          _ptr(bias) if bias is not None else _vp(0), _ptr(out), ctypes.c_long(N), M, N, K, 1 if gelu else 0, int(max_blocks), _stream())
+    _call("s6d_gemm_fp8_mxa", _ptr(a2), K, _ptr(a_mx), _ptr(w8), K, _ptr(w_scale), _ptr(bias), _ptr(out), N, M, N, K, 1 if gelu else 0,
+          int(max_blocks), _stream())
     return out
 
 
@@ -980,13 +966,11 @@ def layernorm_fp8(x, gamma, beta, eps, delta=None):
     y8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     ys = torch.empty(rows, dtype=torch.uint8, device=x.device)
     if delta is None:
-        _call("s6d_layernorm_fp8", _ptr(x), _ptr(gamma), _ptr(beta), ctypes.c_float(eps), ctypes.c_long(rows), int(C), _ptr(y8),
-              _ptr(ys), _stream())
+        _call("s6d_layernorm_fp8", _ptr(x), _ptr(gamma), _ptr(beta), eps, rows, C, _ptr(y8), _ptr(ys), _stream())
         return y8, ys
     _chk(delta, torch.bfloat16, "delta")
     xo = torch.empty_like(x)
-    _call("s6d_add_layernorm_fp8", _ptr(x), _ptr(delta), _ptr(gamma), _ptr(beta), ctypes.c_float(eps), ctypes.c_long(rows), int(C),
-          _ptr(xo), _ptr(y8), _ptr(ys), _stream())
+    _call("s6d_add_layernorm_fp8", _ptr(x), _ptr(delta), _ptr(gamma), _ptr(beta), eps, rows, C, _ptr(xo), _ptr(y8), _ptr(ys), _stream())
     return xo, y8, ys
 
 
@@ -995,7 +979,7 @@ def split_weight(w):
     _chk(w, torch.float32, "w")
     hi = torch.empty(w.shape, dtype=torch.bfloat16, device=w.device)
     lo = torch.empty(w.shape, dtype=torch.bfloat16, device=w.device)
-    _call("s6d_linear_split_weight_f32", _ptr(w), ctypes.c_long(w.numel()), _ptr(hi), _ptr(lo), _stream())
+    _call("s6d_linear_split_weight_f32", _ptr(w), w.numel(), _ptr(hi), _ptr(lo), _stream())
     return hi, lo
 
 
@@ -1031,10 +1015,8 @@ def linear_f32(x, w_hi, w_lo, bias=None, relu=False, residual=None, ln=None):
         _chk(bias, torch.float32, "bias", 1)
         if bias.numel() != N:
             raise ValueError(f"bias must have {N} elements")
-    _call("s6d_linear_f32", _ptr(x2), ctypes.c_long(x2.stride(0)), M, K, _ptr(w_hi), _ptr(w_lo), _ptr(bias) if bias is not None else _vp(0),
-          N, 1 if relu else 0, _ptr(r2) if r2 is not None else _vp(0), ctypes.c_long(r2.stride(0) if r2 is not None else 0),
-          _ptr(g) if g is not None else _vp(0), _ptr(bt) if bt is not None else _vp(0), ctypes.c_float(eps), _ptr(y), ctypes.c_long(N),
-          _stream())
+    _call("s6d_linear_f32", _ptr(x2), x2.stride(0), M, K, _ptr(w_hi), _ptr(w_lo), _ptr(bias), N, 1 if relu else 0, _ptr(r2),
+          r2.stride(0) if r2 is not None else 0, _ptr(g), _ptr(bt), eps, _ptr(y), N, _stream())
     return y.reshape(*x.shape[:-1], N)
 
 
@@ -1044,7 +1026,7 @@ def fragment_weight(w):
     _chk(w, torch.bfloat16, "w", 2)
     w = w.contiguous()
     out = torch.empty_like(w)
-    _call("s6d_linear_fragment_weight", _ptr(w), int(w.shape[0]), int(w.shape[1]), _ptr(out), _stream())
+    _call("s6d_linear_fragment_weight", _ptr(w), w.shape[0], w.shape[1], _ptr(out), _stream())
     return out
 
 
@@ -1073,10 +1055,9 @@ def attn_output_chain(a, x, w1, ln1, we, ws, ln2):
         x2 = x2.contiguous()
     M = a2.shape[0]
     y = torch.empty(M, 256, dtype=torch.float32, device=a.device)
-    _call("s6d_attn_output_chain_f32", _ptr(a2), ctypes.c_long(a2.stride(0)), _ptr(x2), ctypes.c_long(x2.stride(0)), M,
-          _ptr(w1[0]), _ptr(w1[1]), _ptr(w1[2]), _ptr(ln1[0]), _ptr(ln1[1]), ctypes.c_float(ln1[2]),
-          _ptr(we[0]), _ptr(we[1]), _ptr(we[2]), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), _ptr(ln2[0]), _ptr(ln2[1]), ctypes.c_float(ln2[2]),
-          _ptr(y), ctypes.c_long(256), _stream())
+    _call("s6d_attn_output_chain_f32", _ptr(a2), a2.stride(0), _ptr(x2), x2.stride(0), M, _ptr(w1[0]), _ptr(w1[1]), _ptr(w1[2]),
+          _ptr(ln1[0]), _ptr(ln1[1]), ln1[2], _ptr(we[0]), _ptr(we[1]), _ptr(we[2]), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), _ptr(ln2[0]),
+          _ptr(ln2[1]), ln2[2], _ptr(y), 256, _stream())
     return y.reshape(a.shape)
 
 
@@ -1087,8 +1068,7 @@ def layernorm_f32out(x, gamma, beta, eps):
     _chk(beta, torch.float32, "beta", 1)
     C = x.shape[-1]
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    _call("s6d_layernorm_bf16_f32", _ptr(x), _ptr(gamma), _ptr(beta), ctypes.c_float(eps), ctypes.c_long(x.numel() // C), int(C),
-          _ptr(y), _stream())
+    _call("s6d_layernorm_bf16_f32", _ptr(x), _ptr(gamma), _ptr(beta), eps, x.numel() // C, C, _ptr(y), _stream())
     return y
 
 
@@ -1105,9 +1085,8 @@ def add_layernorm(x, delta, gamma, beta, eps):
         xo = torch.empty_like(x)
     else:
         xo = x
-    _call("s6d_add_layernorm_" + sfx, _ptr(x), _ptr(delta) if delta is not None else _vp(0), _ptr(gamma), _ptr(beta),
-          ctypes.c_float(eps), ctypes.c_long(rows), int(C), _ptr(xo) if delta is not None else _vp(0), _ptr(y),
-          _stream())
+    _call("s6d_add_layernorm_" + sfx, _ptr(x), _ptr(delta), _ptr(gamma), _ptr(beta), eps, rows, C, _ptr(xo) if delta is not None else None,
+          _ptr(y), _stream())
     return xo, y
 
 
@@ -1124,11 +1103,11 @@ def geo_embedding(idx4, Wd, bd, Wa, ba, div_term, out_dtype=torch.float32, split
     if split is not None and have("geo_embedding_split"):
         for a, nm in ((split[0], "Wd_hilo"), (split[1], "Wa_hilo")):
             _chk(a, torch.bfloat16, nm, 3)
-        _call("s6d_geo_embedding_split", _ptr(idx4), ctypes.c_long(NP), _ptr(split[0]), _ptr(bd), _ptr(split[1]), _ptr(ba), _ptr(div_term),
-              int(Wd.shape[0]), int(idx4.shape[-1] - 1), _ptr(out), 1 if out_dtype == torch.float16 else 0, _stream())
+        _call("s6d_geo_embedding_split", _ptr(idx4), NP, _ptr(split[0]), _ptr(bd), _ptr(split[1]), _ptr(ba), _ptr(div_term), Wd.shape[0],
+              idx4.shape[-1] - 1, _ptr(out), 1 if out_dtype == torch.float16 else 0, _stream())
         return out
-    _call("s6d_geo_embedding_f32" if out_dtype == torch.float32 else "s6d_geo_embedding_f16", _ptr(idx4), ctypes.c_long(NP), _ptr(Wd),
-          _ptr(bd), _ptr(Wa), _ptr(ba), _ptr(div_term), int(Wd.shape[0]), int(idx4.shape[-1] - 1), _ptr(out), _stream())
+    _call("s6d_geo_embedding_f32" if out_dtype == torch.float32 else "s6d_geo_embedding_f16", _ptr(idx4), NP, _ptr(Wd), _ptr(bd), _ptr(Wa),
+          _ptr(ba), _ptr(div_term), Wd.shape[0], idx4.shape[-1] - 1, _ptr(out), _stream())
     return out
 
 
@@ -1138,14 +1117,11 @@ def fine_assign(atten, pts2):
     _chk(pts2, torch.float32, "pts2", 3)
     B, M1, M2 = atten.shape
     dev = atten.device
-    fn = _lib.lib().s6d_fine_assign_workspace_bytes
-    fn.restype = ctypes.c_long
-    ws = torch.empty(int(fn(B, M1, M2)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_size("s6d_fine_assign_workspace_bytes", B, M1, M2), dtype=torch.uint8, device=dev)
     pred = torch.empty(B, M1 - 1, 3, dtype=torch.float32, device=dev)
     wsum = torch.empty(B, M1 - 1, dtype=torch.float32, device=dev)
     w1 = torch.empty(B, M1 - 1, dtype=torch.float32, device=dev)
-    _call("s6d_fine_assign_f32", _ptr(atten), _ptr(pts2), B, M1, M2, _ptr(ws), _ptr(pred), _ptr(wsum), _ptr(w1),
-          _stream())
+    _call("s6d_fine_assign_f32", _ptr(atten), _ptr(pts2), B, M1, M2, _ptr(ws), _ptr(pred), _ptr(wsum), _ptr(w1), _stream())
     return pred, wsum, w1
 
 
@@ -1159,14 +1135,12 @@ def fine_match(f1, f2, pts2, temp):
     if f2.shape[0] != B or f2.shape[2] != C or tuple(pts2.shape) != (B, M2 - 1, 3):
         raise ValueError(f"fine_match: shapes {tuple(f1.shape)}, {tuple(f2.shape)}, {tuple(pts2.shape)}")
     dev = f1.device
-    fn = _lib.lib().s6d_fine_match_workspace_bytes
-    fn.restype = ctypes.c_long
-    ws = torch.empty(int(fn(B, M1, M2)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_size("s6d_fine_match_workspace_bytes", B, M1, M2), dtype=torch.uint8, device=dev)
     pred = torch.empty(B, M1 - 1, 3, dtype=torch.float32, device=dev)
     wsum = torch.empty(B, M1 - 1, dtype=torch.float32, device=dev)
     w1 = torch.empty(B, M1 - 1, dtype=torch.float32, device=dev)
-    _call("s6d_fine_match_f32", _ptr(f1), _ptr(f2), _ptr(pts2), B, M1, M2, C, ctypes.c_float(1.0 / temp), _ptr(ws),
-          _ptr(pred), _ptr(wsum), _ptr(w1), _stream())
+    _call("s6d_fine_match_f32", _ptr(f1), _ptr(f2), _ptr(pts2), B, M1, M2, C, 1.0 / temp, _ptr(ws), _ptr(pred), _ptr(wsum), _ptr(w1),
+          _stream())
     return pred, wsum, w1
 
 
@@ -1181,8 +1155,7 @@ def pe_group_mlp(pts, idx, W0, b0, W1, b1, W2, b2):
             raise RuntimeError(f"SharedMLP [6,32,64,128] expected, got weight of shape {tuple(w.shape)}")
     B, N, _ = pts.shape
     out = torch.empty(B, N, 128, dtype=torch.float32, device=pts.device)
-    _call("s6d_pe_group_mlp_f32", _ptr(pts), _ptr(idx), B, N, int(idx.shape[2]), *[_ptr(w) for w in ws], _ptr(out),
-          _stream())
+    _call("s6d_pe_group_mlp_f32", _ptr(pts), _ptr(idx), B, N, idx.shape[2], *[_ptr(w) for w in ws], _ptr(out), _stream())
     return out
 
 
@@ -1192,8 +1165,7 @@ def mha(q, k, v, scale):
     (q, ldq), (k, ldk), (v, ldv) = _rows3(q, "q"), _rows3(k, "k"), _rows3(v, "v")
     B, N, C = q.shape
     out = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
-    _call("s6d_mha_strided_f32", _ptr(q), ctypes.c_long(ldq), _ptr(k), ctypes.c_long(ldk), _ptr(v), ctypes.c_long(ldv), B, N,
-          int(k.shape[1]), C, 4, ctypes.c_float(scale), _ptr(out), _stream())
+    _call("s6d_mha_strided_f32", _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, B, N, k.shape[1], C, 4, scale, _ptr(out), _stream())
     return out
 
 
@@ -1204,8 +1176,7 @@ def linear_attn_focus(x, inv_scale, power):
     inv_scale = inv_scale.reshape(-1).contiguous()
     _chk(inv_scale, torch.float32, "inv_scale", 1)
     y = torch.empty_like(x)
-    _call("s6d_linear_attn_focus_f32", _ptr(x), _ptr(inv_scale), ctypes.c_long(x.numel() // x.shape[-1]),
-          int(x.shape[-1]), int(power), _ptr(y), _stream())
+    _call("s6d_linear_attn_focus_f32", _ptr(x), _ptr(inv_scale), x.numel() // x.shape[-1], x.shape[-1], int(power), _ptr(y), _stream())
     return y
 
 
@@ -1224,12 +1195,10 @@ def linear_attention(q_proj, inv_scale, power, k_focused, v):
                              f"strides {tuple(t.stride())}")
     inv_scale = inv_scale.reshape(-1).contiguous()
     _chk(inv_scale, torch.float32, "inv_scale", 1)
-    fn = _lib.lib().s6d_linear_attention_workspace_floats
-    fn.restype = ctypes.c_long
-    ws = torch.empty(int(fn(int(B))), dtype=torch.float32, device=q_proj.device)
+    ws = torch.empty(_size("s6d_linear_attention_workspace_floats", B), dtype=torch.float32, device=q_proj.device)
     out = torch.empty_like(q_proj)
-    _call("s6d_linear_attention_f32", _ptr(q_proj), _ptr(inv_scale), int(power), _ptr(k_focused), ctypes.c_long(k_focused.stride(1)),
-          _ptr(v), ctypes.c_long(v.stride(1)), int(B), int(I), int(J), int(C), _ptr(ws), _ptr(out), _stream())
+    _call("s6d_linear_attention_f32", _ptr(q_proj), _ptr(inv_scale), int(power), _ptr(k_focused), k_focused.stride(1), _ptr(v), v.stride(1),
+          B, I, J, C, _ptr(ws), _ptr(out), _stream())
     return out
 
 
@@ -1271,13 +1240,11 @@ def patch_scores(query, refstore, obj, tmpl, thred, sel=None):
         if obj.shape[0] != S or tmpl.shape[0] != S:
             raise ValueError("patch_scores: obj / tmpl / sel must have one entry per selected proposal")
     _, T, N2, _ = refstore.shape
-    fn = _lib.lib().s6d_patch_scores_workspace_floats
-    fn.restype = ctypes.c_long
-    ws = torch.empty(max(int(fn(S, N1, N2)), 1), dtype=torch.float32, device=query.device)
+    ws = torch.empty(max(_size("s6d_patch_scores_workspace_floats", S, N1, N2), 1), dtype=torch.float32, device=query.device)
     appe = torch.empty(S, dtype=torch.float32, device=query.device)
     ratio = torch.empty(S, dtype=torch.float32, device=query.device)
-    _call("s6d_patch_scores_sel_f32", _ptr(query), _ptr(sel) if sel is not None else _vp(0), _ptr(refstore), _ptr(obj), _ptr(tmpl),
-          S, N1, N2, C, T, ctypes.c_float(thred), _ptr(ws), _ptr(appe), _ptr(ratio), _stream())
+    _call("s6d_patch_scores_sel_f32", _ptr(query), _ptr(sel), _ptr(refstore), _ptr(obj), _ptr(tmpl), S, N1, N2, C, T, thred, _ptr(ws),
+          _ptr(appe), _ptr(ratio), _stream())
     return appe, ratio
 
 
@@ -1307,11 +1274,9 @@ def masked_depth_mean(masks, depth, K, depth_scale, frame=None, sel=None):
             raise ValueError(f"frame indices span [{lo}, {hi}] but there are {depth.shape[0]} frames")
     Kd = K.detach().to(device=masks.device, dtype=torch.float64).contiguous()
     out = torch.empty(S, 3, dtype=torch.float32, device=masks.device)
-    fn = _lib.lib().s6d_masked_depth_mean_workspace_bytes
-    fn.restype = ctypes.c_long
-    ws = torch.empty(max(int(fn(S, H, W)), 8), dtype=torch.uint8, device=masks.device)
-    _call("s6d_masked_depth_mean_sel_f32", _ptr(masks), _ptr(sel) if sel is not None else _vp(0), _ptr(depth),
-          _ptr(frame) if frame is not None else _vp(0), S, H, W, ctypes.c_float(depth_scale), _ptr(Kd), _ptr(ws), _ptr(out), _stream())
+    ws = torch.empty(max(_size("s6d_masked_depth_mean_workspace_bytes", S, H, W), 8), dtype=torch.uint8, device=masks.device)
+    _call("s6d_masked_depth_mean_sel_f32", _ptr(masks), _ptr(sel), _ptr(depth), _ptr(frame), S, H, W, depth_scale, _ptr(Kd), _ptr(ws),
+          _ptr(out), _stream())
     return out
 
 
@@ -1326,8 +1291,8 @@ def project_bbox(pointcloud, poses, obj, tmpl, trans, K, H, W, frame=None):
     S, N = obj.shape[0], pointcloud.shape[1]
     uv = torch.empty(S, N, 2, dtype=torch.int32, device=trans.device)
     bbox = torch.empty(S, 4, dtype=torch.int32, device=trans.device)
-    _call("s6d_project_bbox_frames_f32", _ptr(pointcloud), _ptr(poses), _ptr(obj), _ptr(tmpl), _ptr(trans), _ptr(K),
-          _ptr(frame) if frame is not None else _vp(0), S, N, int(H), int(W), _ptr(uv), _ptr(bbox), _stream())
+    _call("s6d_project_bbox_frames_f32", _ptr(pointcloud), _ptr(poses), _ptr(obj), _ptr(tmpl), _ptr(trans), _ptr(K), _ptr(frame), S, N,
+          int(H), int(W), _ptr(uv), _ptr(bbox), _stream())
     return uv, bbox
 
 
@@ -1342,7 +1307,7 @@ def have(name):
         sym = {"rpe_attention": "s6d_rpe_attention_f32", "rpe_attention_packed": "s6d_rpe_attention_packed_f32", "geo_embedding": "s6d_geo_embedding_f32", "geo_embedding_f16": "s6d_geo_embedding_f16", "geo_embedding_split": "s6d_geo_embedding_split",
                "fine_assign": "s6d_fine_assign_f32", "fine_match": "s6d_fine_match_f32", "pem_pre": "s6d_pem_compact_cloud_f32", "coarse_sample": "s6d_coarse_sample_f32", "upsample_gather": "s6d_upsample_gather_f32",
                "min_dist": "s6d_min_dist_f32", "rot_from_h": "s6d_rot_from_h_f32", "weighted_procrustes": "s6d_weighted_procrustes_f32", "add_layernorm": "s6d_add_layernorm_bf16", "gemm_bf16": "s6d_gemm_bf16", "gemm_bf16_res": "s6d_gemm_bf16_res", "gemm_bf16_lnfold": "s6d_gemm_bf16_lnfold", "gemm_f16": "s6d_gemm_f16", "gemm_fp8": "s6d_gemm_fp8", "layernorm_fp8": "s6d_layernorm_fp8", "layernorm_f32out": "s6d_layernorm_bf16_f32", "linear_f32": "s6d_linear_f32", "attn_output_chain": "s6d_attn_output_chain_f32", "win_attention": "s6d_win_attention_layout_bf16",
-               "glb_attention": "s6d_glb_attention_bf16", "pairwise_cosine": "s6d_pairwise_cosine_f32",
+               "pairwise_cosine": "s6d_pairwise_cosine_f32",
                "patch_scores": "s6d_patch_scores_sel_f32", "pose_hypotheses": "s6d_pose_hypotheses_f32",
                "pe_group": "s6d_pe_group_mlp_f32", "masked_depth_mean": "s6d_masked_depth_mean_sel_f32",
                "semantic_select": "s6d_semantic_select_f32", "seq_attention": "s6d_seq_attention_bf16", "sam_preprocess": "s6d_sam_preprocess_f32", "im2col3x3": "s6d_im2col3x3_b16", "nonfinite_rows": "s6d_nonfinite_rows_f32", "patchify": "s6d_patchify_b16", "crop_resize_pad": "s6d_crop_resize_pad_f32", "samdec_img2tok": "s6d_samdec_img2tok_bf16", "samdec_img2tok_raw": "s6d_samdec_img2tok_raw_bf16", "samdec_tok2img": "s6d_samdec_tok2img_f32", "samdec_tok2img_raw": "s6d_samdec_tok2img_raw_bf16", "sam_mask_post": "s6d_sam_mask_post_sel_f32", "gemm_fp8_mx": "s6d_gemm_fp8_mxa", "nms": "s6d_nms_f32", "samdec_upscale_heads": "s6d_samdec_upscale_heads_bf16", "samdec_tokens": "s6d_samdec_tokens_post_bf16", "samdec_token_folds": "s6d_samdec_tokens_post_bf16", "mha": "s6d_mha_f32",

@@ -18,11 +18,9 @@ def test_library_loads_and_exports_every_declared_symbol():
 def test_argument_validation_without_a_gpu():
     """Entry points validate sizes/pointers before touching the device: callable on a CPU-only host."""
     L = _lib.lib()
-    L.s6d_fps_f32.restype = ctypes.c_int
     assert L.s6d_fps_f32(None, 1, 0, 1, None, None, None) == -1          # N <= 0
     assert L.s6d_fps_f32(None, 0, 10, 4, None, None, None) == 0           # B == 0: nothing to do
     assert L.s6d_fps_f32(None, 1, 10, 4, None, None, None) == -1          # null pointers
-    L.s6d_rpe_attention_f32.restype = ctypes.c_int
     assert L.s6d_rpe_attention_f32(None, None, None, None, None, None, 1, 197, 128, 4, ctypes.c_float(1.0), None, None) == -3
 
 
@@ -32,9 +30,6 @@ def test_round3_entry_points_validate_shapes_without_a_gpu():
     L = _lib.lib()
     p = ctypes.c_void_p(4096)
     lng, flt = ctypes.c_long, ctypes.c_float
-    for fn in ("s6d_gemm_bf16_lnfold", "s6d_gemm_bf16_res", "s6d_ln_stats_finalize", "s6d_row_stats_bf16", "s6d_linear_attention_f32",
-               "s6d_rpe_attention_strided_f32", "s6d_mha_strided_f32"):
-        getattr(L, fn).restype = ctypes.c_int
     # N % 256 != 0: the 256 x 256-tile kernel only
     assert L.s6d_gemm_bf16_lnfold(p, lng(64), p, p, lng(64), p, p, p, lng(128), 256, 128, 64, 0, 0, 0, None) == -3
     assert L.s6d_gemm_bf16_lnfold(p, lng(64), p, p, lng(64), p, p, p, lng(256), 256, 256, 64, 2, 0, 0, None) == -1       # gelu flag
@@ -62,30 +57,96 @@ def test_ops_refuse_cpu_tensors():
 
 
 def test_every_entry_point_refuses_null_operands():
-    """Generated from the header: each `int s6d_*(...)` prototype is called with NULL for every pointer and small positive
-    sizes.  Every one must come back with S6D_EINVAL / S6D_EUNSUPPORTED before anything is dereferenced or launched
-    (this host has no device, so a launch attempt would surface as S6D_ELAUNCH = -2)."""
-    import os
-    import re
-
+    """Generated from the header (_lib.prototypes()): each `int s6d_*(...)` entry point with a pointer parameter is called with
+    NULL for every pointer and small positive sizes.  Every one must come back with S6D_EINVAL / S6D_EUNSUPPORTED before anything
+    is dereferenced or launched (this host has no device, so a launch attempt would surface as S6D_ELAUNCH = -2)."""
     L = _lib.lib()
-    hdr = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "sam6d_hip.h")
-    src = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
-    protos = re.findall(r"\bint\s+(s6d_\w+)\s*\(([^)]*)\)\s*;", src)
-    assert len(protos) >= 28
-    kinds = {"float": lambda: ctypes.c_float(1.0), "double": lambda: ctypes.c_double(1.0), "long": lambda: ctypes.c_long(16),
-             "int": lambda: ctypes.c_int(16)}
-    rcs = {}
-    for name, args in protos:
-        if args.strip() == "void" or "*" not in args:          # no operand to refuse (s6d_version, s6d_set_persistent_grid_limit)
-            continue
-        vals = []
-        for a in (x.strip() for x in args.split(",")):
-            vals.append(ctypes.c_void_p(0) if "*" in a else kinds[a.split()[0]]())
-        fn = getattr(L, name)
-        fn.restype = ctypes.c_int
-        rcs[name] = fn(*vals)
+    vals = {ctypes.c_void_p: None, ctypes.c_float: 1.0, ctypes.c_double: 1.0, ctypes.c_long: 16, ctypes.c_int: 16}
+    # (no pointer = no operand to refuse: s6d_version, the s6d_set_* switches, the workspace sizes)
+    protos = {n: a for n, (r, a) in _lib.prototypes().items() if r is ctypes.c_int and ctypes.c_void_p in a}
+    assert len(protos) == len(_lib.declared_symbols()) - sum(r is not ctypes.c_int or ctypes.c_void_p not in a
+                                                             for r, a in _lib.prototypes().values()) >= 28
+    rcs = {name: getattr(L, name)(*[vals[t] for t in args]) for name, args in protos.items()}
     assert all(rc in (-1, -3) for rc in rcs.values()), rcs
+
+
+def test_header_is_the_prototype_table():
+    """Every declared entry point has a prototype, the loaded library carries it, and a type the parser does not know is an error
+    that names the prototype (a header string with one injected declaration; the header itself is not touched)."""
+    import os
+
+    import pytest
+    protos = _lib.prototypes()
+    assert sorted(protos) == _lib.declared_symbols() and len(protos) >= 25
+    assert {r for r, _ in protos.values()} == {ctypes.c_int, ctypes.c_long, ctypes.c_char_p}
+    assert {t for _, a in protos.values() for t in a} == {ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float}
+    assert protos["s6d_fps_f32"] == (ctypes.c_int, (ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int) + (ctypes.c_void_p,) * 3)
+    assert protos["s6d_version"] == (ctypes.c_int, ()) and protos["s6d_strerror"] == (ctypes.c_char_p, (ctypes.c_int,))
+    assert protos["s6d_nms_workspace_bytes"] == (ctypes.c_long, (ctypes.c_int,))
+    L = _lib.lib()
+    for name, (restype, argtypes) in protos.items():
+        assert getattr(L, name).restype is restype and tuple(getattr(L, name).argtypes) == argtypes, name
+    hdr = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "sam6d_hip.h")).read()
+    assert _lib.parse_header(hdr) == (_lib.abi_version(), protos)
+    for decl in ("int s6d_new_thing(const float *x, size_t n, void *stream);", "int64_t s6d_new_thing(const float *x);",
+                 "int s6d_new_thing(unsigned int n);"):
+        with pytest.raises(ValueError, match="s6d_new_thing"):
+            _lib.parse_header(hdr.replace("int s6d_version(void);", decl + "\nint s6d_version(void);"))
+    _, more = _lib.parse_header(hdr.replace("int s6d_version(void);", "long s6d_new_thing(const double *const x, double y, const int n);\n"
+                                                                      "int s6d_version(void);"))
+    assert more["s6d_new_thing"] == (ctypes.c_long, (ctypes.c_void_p, ctypes.c_double, ctypes.c_int)) and len(more) == len(protos) + 1
+
+
+def test_ops_name_only_declared_entry_points():
+    """Static: every string literal beginning `s6d_` that reaches _call / _size in sam6d_amd/ops.py, and every value of the have()
+    map, is a declared entry point -- or, where the name is finished at run time ("s6d_seq_attention_" + suffix), a prefix of one."""
+    import ast
+    import os
+
+    from sam6d_amd import ops
+    declared = _lib.declared_symbols()
+    tree = ast.parse(open(os.path.splitext(ops.__file__)[0] + ".py").read())
+    names, prefixes = set(), set()
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Call) and getattr(node.func, "id", None) in ("_call", "_size"):
+            lits = [c.value for c in ast.walk(node.args[0]) if isinstance(c, ast.Constant) and isinstance(c.value, str)]
+            assert lits and all(v.startswith("s6d_") for v in lits), (node.lineno, lits)
+            (prefixes if isinstance(node.args[0], ast.BinOp) else names).update(lits)
+        if isinstance(node, ast.FunctionDef) and node.name == "have":
+            maps = [d for d in ast.walk(node) if isinstance(d, ast.Dict)]
+            assert len(maps) == 1 and len(maps[0].values) >= 40
+            names.update(v.value for v in maps[0].values)
+    assert len(names) >= 70 and prefixes
+    assert not [n for n in names if n not in declared], [n for n in names if n not in declared]
+    assert all(any(d.startswith(p) and d != p for d in declared) for p in prefixes), prefixes
+    every = {c.value for c in ast.walk(tree) if isinstance(c, ast.Constant) and isinstance(c.value, str) and c.value.startswith("s6d_")}
+    assert every == names | prefixes, every - names - prefixes          # no entry-point name goes to the library by another road
+
+
+def test_calls_are_checked_against_the_prototype():
+    """One argument too many or too few is a TypeError, a float where a pointer or an int is declared a ctypes.ArgumentError, an
+    unknown name an AttributeError: all before the library is entered (s6d_fps_f32 with B = 0 is otherwise a no-op returning 0)."""
+    import pytest
+
+    from sam6d_amd import ops
+    args = (None, 0, 10, 4, None, None, None)
+    ops._call("s6d_fps_f32", *args)
+    with pytest.raises(TypeError, match="s6d_fps_f32 takes 7 arguments"):
+        ops._call("s6d_fps_f32", *args, None)
+    with pytest.raises(TypeError, match="s6d_fps_f32 takes 7 arguments"):
+        ops._call("s6d_fps_f32", *args[:-1])
+    with pytest.raises(TypeError):
+        _lib.lib().s6d_fps_f32(*args[:-1])                     # (too few: ctypes' own check on the typed function)
+    for bad in ((1.5,) + args[1:], args[:1] + (0.0,) + args[2:], args[:3] + (4.0,) + args[4:]):
+        with pytest.raises(ctypes.ArgumentError):
+            ops._call("s6d_fps_f32", *bad)
+    with pytest.raises(AttributeError, match="s6d_no_such_entry"):
+        ops._call("s6d_no_such_entry", None)
+    with pytest.raises(_lib.S6DError, match="s6d_fps_f32"):
+        ops._call("s6d_fps_f32", None, 1, 0, 1, None, None, None)          # N <= 0: the code still goes through _lib.check
+    assert ops._size("s6d_nms_workspace_bytes", 100000) > 2 ** 30          # a `long` result comes back whole
+    with pytest.raises(TypeError, match="s6d_nms_workspace_bytes takes 1 arguments"):
+        ops._size("s6d_nms_workspace_bytes", 1, 2)
 
 
 def test_product_library_carries_no_emulator_code():

@@ -157,7 +157,6 @@ def test_round2_entry_points_reject_bad_arguments_and_accept_empty_batches(ops):
     L = _lib.lib()
     null, one = ctypes.c_void_p(0), ctypes.c_float(10.0)
     lg = ctypes.c_long
-    L.s6d_fine_match_workspace_bytes.restype = ctypes.c_long
     ok = [
         L.s6d_gemm_bf16(null, lg(1280), null, lg(1280), null, null, lg(1280), 0, 1280, 1280, 0, 0, null),
         L.s6d_fine_match_f32(null, null, null, 0, 2049, 2049, 256, one, null, null, null, null, null),
