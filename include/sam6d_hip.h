@@ -30,7 +30,7 @@ extern "C" {
 
 /* Bumped whenever a signature in this header changes; the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 124
+#define S6D_ABI_VERSION 125
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -410,6 +410,40 @@ int s6d_geo_embedding_split(const float *idx4, long NP, const void *Wd_hilo, con
  * slices in LDS by LDS-DMA, one barrier per k-step, no LDS bank conflicts; profiles/r06_geo_embed.md).  Same bits either way.
  * Other values: S6D_EINVAL. */
 int s6d_set_geo_embed_form(int form);
+
+/* The index stage of the geometric structure embedding, straight from the points: get_embedding_indices,
+ * Pose_Estimation_Model/model/transformer.py:303-332.  points (B,N,3) f32, 4 <= N <= 256 (the cloud and a lane's four candidate
+ * distances are held in LDS / registers for that range; S6D_EINVAL beyond it, and for N < 4: three neighbours besides the anchor).
+ * All fp32, every multiply, add and subtract rounded on its own (no fused multiply-add), so the values depend neither on B nor on
+ * the launch geometry:
+ *   distance   diff = p_m - p_n per component; dist(n,m) = sqrt((dx*dx + dy*dy) + dz*dz), correctly rounded sqrt -- the DIRECT form,
+ *              not the reference's expanded square |x|^2 - 2 x.y + |y|^2 (which leaves dist(n,n) at ~1e-3 instead of 0):
+ *              dist(n,n) = 0 exactly.  d_idx = dist / sigma_d, correctly rounded division.
+ *   neighbours the three smallest dist(n,m) over m != n; TIES GO TO THE LOWER INDEX m (torch.topk leaves the order of ties open).
+ *              The anchor is excluded by its index, not by its value: the reference drops rank 0 of topk(k + 1), which for a
+ *              duplicated point may be the duplicate instead of the anchor -- the neighbour VECTORS are equal either way.
+ *   angles     ref = p_knn - p_n, anc = p_m - p_n, c = ref x anc (c_x = r_y a_z - r_z a_y, ...);
+ *              a_idx = atan2f(sqrt((cx*cx + cy*cy) + cz*cz), (rx*ax + ry*ay) + rz*az) * factor_a, and 0 where both arguments
+ *              are 0 (m == n, duplicated points).
+ * s6d_geo_knn_f32: knn (B,N,3) i32, the neighbours of every anchor, nearest first.
+ * s6d_geo_indices_f32: idx4 (B,N,N,4) f32 = [d_idx, a_idx_0..2] of pair (n,m) as s6d_geo_embedding_* read it. */
+int s6d_geo_knn_f32(const float *points, int B, int N, int32_t *knn, void *stream);
+int s6d_geo_indices_f32(const float *points, int B, int N, float sigma_d, float factor_a, float *idx4, void *stream);
+/* The three s6d_geo_embedding_* entry points fed from the points: the four indices of a pair are computed in the kernels' prologue
+ * by the device function s6d_geo_indices_f32 uses (the same bits as s6d_geo_embedding_*(s6d_geo_indices_f32(points)), and no
+ * (B,N,N,.) tensor besides `out` is read or written).  `knn` is caller-provided scratch of B*N*3 int32, written by one small launch
+ * in front of the embedding kernel (the neighbours, as s6d_geo_knn_f32 gives them).  out (B,N,N,C).  Same limits on N; C = 256,
+ * K = 3.  The split form honours s6d_set_geo_embed_form.
+ * ref: transformer.py:303-332 (indices) and :334-349 (embedding). */
+int s6d_geo_embedding_points_f32(const float *points, int B, int N, float sigma_d, float factor_a, int32_t *knn, const float *Wd,
+                                 const float *bd, const float *Wa, const float *ba, const float *div_term, int C, int K, float *out,
+                                 void *stream);
+int s6d_geo_embedding_points_f16(const float *points, int B, int N, float sigma_d, float factor_a, int32_t *knn, const float *Wd,
+                                 const float *bd, const float *Wa, const float *ba, const float *div_term, int C, int K,
+                                 void *out_f16, void *stream);
+int s6d_geo_embedding_points_split(const float *points, int B, int N, float sigma_d, float factor_a, int32_t *knn,
+                                   const void *Wd_hilo, const float *bd, const void *Wa_hilo, const float *ba, const float *div_term,
+                                   int C, int K, void *out, int out_f16, void *stream);
 
 /* Fused fp32 Linear of the point transformer:  y = LN( res + act( x W^T + b ) )  with every stage optional.
  * x (M,K) f32 row stride ldx; W given as its bf16 hi / lo parts (N,K) each, made once per weight version by

@@ -11,6 +11,9 @@
 // once.  Workgroup = 64 point pairs x 256 outputs, 8 waves: wave (mt, nh) owns pairs [16mt,16mt+16) and
 // outputs [128nh, 128nh+128).  Per 32-channel k-step: all waves first build the shared operands in LDS
 // (sincos fragments hi/lo, weight slices hi/lo), then run 96 MFMAs each.
+// The stage in front of it -- get_embedding_indices, transformer.py:303-332: pair distances, the three nearest neighbours of every
+// anchor, the angles -- is here too: geo_indices_kernel (points -> idx4 or -> the neighbour table) and a points-fed prologue of the
+// embedding kernels, so that no (B,N,N,.) tensor besides the embedding exists (s6d_geo_embedding_points_*).
 #include "s6d_common.h"
 
 namespace s6d {
@@ -41,6 +44,150 @@ __device__ __forceinline__ void fast_sincos(float a, float &sn, float &cs) {
   cs = __builtin_amdgcn_cosf(rev);
 }
 
+// ---- the index stage from the points (get_embedding_indices, transformer.py:303-332) ---------------------------------------------
+// include/sam6d_hip.h (s6d_geo_indices_f32) states the formulas.  Rounding: the function below is compiled with floating-point
+// contraction OFF, so every multiply, add and subtract is its own IEEE operation in the order written (the library is built without
+// fast-math); sqrtf and `/` are the correctly rounded forms (the compiler's default for HIP without fast-math: v_sqrt_f32 / v_rcp_f32
+// plus the correction steps -- NOT __fsqrt_rn, which is the bare v_sqrt_f32 in this toolchain); atan2f is the device library's (no fast-math
+// variant; a few ulp).  The values therefore depend on the three points alone -- not on B, the launch geometry or the kernel the
+// function is inlined into: geo_indices_kernel and the points-fed prologues of the two embedding kernels call THIS function.
+__device__ __forceinline__ float geo_pair_dist(float nx, float ny, float nz, float mx, float my, float mz) {
+#pragma clang fp contract(off)
+  const float dx = mx - nx, dy = my - ny, dz = mz - nz;
+  return sqrtf((dx * dx + dy * dy) + dz * dz);
+}
+// value e of pair (n, m): e = 0 the distance index, e = 1..3 the angle index against neighbour k = e - 1 of anchor n (point k*)
+__device__ __forceinline__ float geo_index_value(int e, float nx, float ny, float nz, float mx, float my, float mz, float kx, float ky,
+                                                 float kz, float sigma_d, float factor_a) {
+#pragma clang fp contract(off)
+  if (e == 0) return geo_pair_dist(nx, ny, nz, mx, my, mz) / sigma_d;
+  const float ax = mx - nx, ay = my - ny, az = mz - nz;                // anc = p_m - p_n
+  const float rx = kx - nx, ry = ky - ny, rz = kz - nz;                // ref = p_knn - p_n
+  const float cx = ry * az - rz * ay, cy = rz * ax - rx * az, cz = rx * ay - ry * ax;
+  const float sn = sqrtf((cx * cx + cy * cy) + cz * cz);
+  const float cs = (rx * ax + ry * ay) + rz * az;
+  if (sn == 0.f && cs == 0.f) return 0.f;                              // anc == 0 or ref == 0 (cs may be -0: atan2f(0, -0) = pi)
+  return atan2f(sn, cs) * factor_a;
+}
+
+constexpr int GEOIDX_MAX_N = 256;                                      // a lane keeps GEOIDX_MAX_N / 64 candidates in registers
+constexpr int GEOIDX_THREADS = 256;                                    // four waves
+constexpr int GEOIDX_ANCHORS = 16;                                     // anchors per workgroup, four per wave
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffull), o);
+    const unsigned hi = __shfl_xor((unsigned)(v >> 32), o);
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+// The three nearest neighbours of anchor n, found by ONE wave (all 64 lanes call this): lane l holds the candidates m = l + 64 j as
+// keys (bits of dist(n,m)) << 32 | m -- distances are >= +0, so the unsigned order of the keys is (distance, then index): three
+// rounds of a cross-lane minimum, each followed by the removal of the winner, give the three smallest distances with ties to the
+// lower index.  The anchor itself and m >= N carry the all-ones key, which no candidate reaches (m < 256): with N >= 4 it never wins.
+__device__ __forceinline__ void geo_wave_knn3(const float *sx, const float *sy, const float *sz, int N, int n, int lane, int (&nb)[3]) {
+  const float nx = sx[n], ny = sy[n], nz = sz[n];
+  unsigned long long key[GEOIDX_MAX_N / 64];
+#pragma unroll
+  for (int j = 0; j < GEOIDX_MAX_N / 64; ++j) {
+    const int m = lane + 64 * j;
+    key[j] = ~0ull;
+    if (m < N && m != n) key[j] = ((unsigned long long)__float_as_uint(geo_pair_dist(nx, ny, nz, sx[m], sy[m], sz[m])) << 32) | (unsigned)m;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    unsigned long long best = key[0];
+#pragma unroll
+    for (int j = 1; j < GEOIDX_MAX_N / 64; ++j) best = key[j] < best ? key[j] : best;
+    best = wave_min_u64(best);
+    nb[r] = (int)(unsigned)(best & 0xffffffffull);
+#pragma unroll
+    for (int j = 0; j < GEOIDX_MAX_N / 64; ++j)
+      if (key[j] == best) key[j] = ~0ull;
+  }
+}
+
+// FULL: points -> idx4 (B,N,N,4) (the standalone form, and for callers that keep idx4); else only knn (B,N,3), the pre-kernel of the
+// points-fed embedding.  Workgroup (b, tile of 16 anchors): the cloud of b in LDS (3 x 1 KB), a wave per anchor in turn; in the FULL
+// form the wave then writes the anchor's row, lane l the pairs m = l, l + 64, ... as one float4 each.
+template <bool FULL>
+__global__ __launch_bounds__(GEOIDX_THREADS) void geo_indices_kernel(const float *__restrict__ points, int N, int tiles, float sigma_d,
+                                                                    float factor_a, float *__restrict__ idx4, int32_t *__restrict__ knn) {
+  __shared__ float sx[GEOIDX_MAX_N], sy[GEOIDX_MAX_N], sz[GEOIDX_MAX_N];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int b = blockIdx.x / tiles, n0 = (blockIdx.x - b * tiles) * GEOIDX_ANCHORS;
+  const float *P = points + (size_t)b * N * 3;
+  for (int i = tid; i < N; i += GEOIDX_THREADS) {
+    sx[i] = P[3 * i];
+    sy[i] = P[3 * i + 1];
+    sz[i] = P[3 * i + 2];
+  }
+  __syncthreads();
+  for (int a = wave; a < GEOIDX_ANCHORS; a += GEOIDX_THREADS / 64) {
+    const int n = n0 + a;
+    if (n >= N) break;                                               // the same for every lane of the wave
+    int nb[3];
+    geo_wave_knn3(sx, sy, sz, N, n, lane, nb);
+    if (!FULL) {
+      if (lane == 0) {
+        int32_t *o = knn + ((size_t)b * N + n) * 3;
+        o[0] = nb[0];
+        o[1] = nb[1];
+        o[2] = nb[2];
+      }
+      continue;
+    }
+    const float nx = sx[n], ny = sy[n], nz = sz[n];
+    float4 *row = reinterpret_cast<float4 *>(idx4) + ((size_t)b * N + n) * N;
+    for (int m = lane; m < N; m += 64) {
+      float4 v;
+      v.x = geo_index_value(0, nx, ny, nz, sx[m], sy[m], sz[m], 0.f, 0.f, 0.f, sigma_d, factor_a);
+      v.y = geo_index_value(1, nx, ny, nz, sx[m], sy[m], sz[m], sx[nb[0]], sy[nb[0]], sz[nb[0]], sigma_d, factor_a);
+      v.z = geo_index_value(2, nx, ny, nz, sx[m], sy[m], sz[m], sx[nb[1]], sy[nb[1]], sz[nb[1]], sigma_d, factor_a);
+      v.w = geo_index_value(3, nx, ny, nz, sx[m], sy[m], sz[m], sx[nb[2]], sy[nb[2]], sz[nb[2]], sigma_d, factor_a);
+      row[m] = v;
+    }
+  }
+}
+
+// Where the embedding kernels take the four indices of pair pr from: the idx4 tensor, or the points and the neighbour table
+// (geo_indices_kernel<false>): (b, n, m) from the flat pair index, then the function geo_indices_kernel<true> fills idx4 with.
+// Read once per thread, in the prologue: nothing of it is live in the k-loop.
+struct GeoFromIdx {
+  const float *idx4;
+  long NP;
+  __device__ __forceinline__ float value(long pr, int e) const { return idx4[pr * 4 + e]; }
+};
+struct GeoFromPoints {
+  const float *points;
+  const int32_t *knn;
+  long NP;
+  int N;
+  float sigma_d, factor_a;
+  __device__ __forceinline__ float value(long pr, int e) const {
+    const int NN = N * N;
+    const int b = (int)(pr / NN), r = (int)(pr - (long)b * NN);
+    const int n = r / N, m = r - n * N;
+    const float *P = points + (size_t)b * N * 3;
+    const int k = e ? knn[((size_t)b * N + n) * 3 + (e - 1)] : n;
+    float x = geo_index_value(e, P[3 * n], P[3 * n + 1], P[3 * n + 2], P[3 * m], P[3 * m + 1], P[3 * m + 2], P[3 * k], P[3 * k + 1],
+                              P[3 * k + 2], sigma_d, factor_a);
+    // x must reach the k-loop as the materialised fp32 value an idx4 load would deliver.  Its last producers -- the multiply by
+    // factor_a, the division by sigma_d, the select on the zero case -- are compiled with contraction off; its consumer, the product
+    // x * div_term[j] of the sinusoids, with the kernel's default (contraction allowed).  The empty statement keeps the optimiser from
+    // looking through x and combining the two sides (during development a prologue without it gave 1-ulp different sinusoid arguments in
+    // geo_embed2_kernel; profiles/geo_from_points.md); no instruction, no register.
+#ifndef HIPEMU
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+  }
+};
+
 constexpr int GEO_C = 256;          // hidden dim
 constexpr int GEO_ROW = 40;         // LDS row stride (bf16): 32 channels + 8 pad (80 B = 5 chunks of 16 B)
 // A ds_read_b128 lane group is {rows 0-3,12-15 reading chunk g} + {rows 4-11 reading chunk g + 1}: with any odd row stride these
@@ -67,8 +214,9 @@ constexpr int GEO_LDS_ELEMS = OFF_AL + 4 * GEO_PAIRS * GEO_ROW;    // 61440 elem
 // PRE (round 5): the weights arrive as their bf16 hi / lo parts (s6d_linear_split_weight_f32, made once per weight version by the
 // caller) -- Wd / Wa then point at [hi (C x C) | lo (C x C)] bf16.  Until then EVERY workgroup split the same two 256 x 256 fp32
 // matrices again in every k-step: ~200 of a thread's ~400 vector instructions per k-step beside 96 matrix instructions per wave.
-template <bool HALF, bool PRE>
-__global__ __launch_bounds__(GEO_THREADS) void geo_embed_kernel(const float *__restrict__ idx4, long NP,
+// SRC: GeoFromIdx (idx4 as a tensor) or GeoFromPoints (the indices computed here, in the prologue).
+template <bool HALF, bool PRE, class SRC>
+__global__ __launch_bounds__(GEO_THREADS) void geo_embed_kernel(const SRC src,
                                                                const float *__restrict__ Wd, const float *__restrict__ bd,
                                                                const float *__restrict__ Wa, const float *__restrict__ ba,
                                                                const float *__restrict__ div_term, void *__restrict__ outv) {
@@ -77,7 +225,7 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed_kernel(const float *__r
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 15, g = lane >> 4;
   const int mt = wave & 3, nh = wave >> 2;
-  const long pair0 = (long)blockIdx.x * GEO_PAIRS;
+  const long pair0 = (long)blockIdx.x * GEO_PAIRS, NP = src.NP;
 
   // ---- per-thread constants of the operand builders -------------------------------------------------
   // weights: each k-step slice is 256 rows x 32 fp32 per matrix = 2048 float4 per matrix; 512 threads x 4
@@ -91,7 +239,7 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed_kernel(const float *__r
     item_e[n] = (it >> 2) & 3;
     item_p[n] = it >> 4;
     const long pr = min(pair0 + item_p[n], NP - 1);
-    xval[n] = idx4[pr * 4 + item_e[n]];
+    xval[n] = src.value(pr, item_e[n]);
   }
   float4 wreg[8];                                                  // prefetched weight slice (4 of W_d, 4 of W_a); PRE: 8 x 16 bytes of bf16
   auto wload = [&](int ks) {
@@ -264,8 +412,8 @@ constexpr int G2_LDS_BYTES = 2 * G2_STAGE * 2;                     // 128 KB
 #endif
 __device__ __forceinline__ int g2_swz(int row) { return ((row >> 3) & 1) << 1; }
 
-template <bool HALF>
-__global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const float *__restrict__ idx4, long NP, const u16 *__restrict__ Wd,
+template <bool HALF, class SRC>
+__global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const SRC src, const u16 *__restrict__ Wd,
                                                                 const float *__restrict__ bd, const u16 *__restrict__ Wa,
                                                                 const float *__restrict__ ba, const float *__restrict__ div_term,
                                                                 void *__restrict__ outv) {
@@ -274,12 +422,12 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const float *__
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 15, g = lane >> 4;
   const int mt = wave & 3, nh = wave >> 2;
-  const long pair0 = (long)blockIdx.x * GEO_PAIRS;
+  const long pair0 = (long)blockIdx.x * GEO_PAIRS, NP = src.NP;
   float xv[4];
   {
     const long pr = min(pair0 + mt * 16 + c, NP - 1);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) xv[e] = idx4[pr * 4 + e];
+    for (int e = 0; e < 4; ++e) xv[e] = src.value(pr, e);
   }
   // weight slice of k-step ks -> stage: LDS-DMA (global_load_lds_dwordx4: no registers, no ds_write).  A piece = one part's 16 rows
   // x 64 B = 1 KiB per wave instruction; lane l of wave w lands at element it = 64 w + l (+ 512 for the second piece) of the part's
@@ -428,56 +576,132 @@ extern "C" int s6d_set_geo_embed_form(int form) {
   return S6D_OK;
 }
 
-template <bool HALF, bool PRE>
-static void geo_launch_t(const float *idx4, long NP, const float *Wd, const float *bd, const float *Wa, const float *ba,
-                         const float *div_term, void *out, void *stream) {
+template <bool HALF, bool PRE, class SRC>
+static void geo_launch_t(const SRC &src, const float *Wd, const float *bd, const float *Wa, const float *ba, const float *div_term,
+                         void *out, void *stream) {
   const size_t lds = (size_t)GEO_LDS_ELEMS * 2;
-  const unsigned grid = (unsigned)((NP + GEO_PAIRS - 1) / GEO_PAIRS);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&geo_embed_kernel<HALF, PRE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((geo_embed_kernel<HALF, PRE>), dim3(grid), dim3(GEO_THREADS), lds, as_stream(stream), idx4, NP, Wd, bd, Wa, ba, div_term, out);
+  const unsigned grid = (unsigned)((src.NP + GEO_PAIRS - 1) / GEO_PAIRS);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&geo_embed_kernel<HALF, PRE, SRC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((geo_embed_kernel<HALF, PRE, SRC>), dim3(grid), dim3(GEO_THREADS), lds, as_stream(stream), src, Wd, bd, Wa, ba, div_term, out);
 }
 
-static int geo_launch(const float *idx4, long NP, const void *Wd, const float *bd, const void *Wa, const float *ba,
-                      const float *div_term, int C, int K, void *out, bool half, bool pre, void *stream) {
-  if (NP < 0) return S6D_EINVAL;
-  if (C != GEO_C || K != 3) return S6D_EUNSUPPORTED;      // released model: hidden_dim 256, angle_k 3
-  if (NP == 0) return S6D_OK;
-  if (!idx4 || !Wd || !bd || !Wa || !ba || !div_term || !out) return S6D_EINVAL;
+template <bool HALF, class SRC>
+static void geo_launch2_t(const SRC &src, const u16 *Wd, const float *bd, const u16 *Wa, const float *ba, const float *div_term, void *out,
+                          void *stream) {
+  const unsigned grid = (unsigned)((src.NP + GEO_PAIRS - 1) / GEO_PAIRS);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&geo_embed2_kernel<HALF, SRC>), hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
+  hipLaunchKernelGGL((geo_embed2_kernel<HALF, SRC>), dim3(grid), dim3(GEO_THREADS), G2_LDS_BYTES, as_stream(stream), src, Wd, bd, Wa, ba, div_term, out);
+}
+
+// the embedding kernel over src (its own operands are checked by the caller)
+template <class SRC>
+static int geo_launch(const SRC &src, const void *Wd, const float *bd, const void *Wa, const float *ba, const float *div_term, void *out,
+                      bool half, bool pre, void *stream) {
+  if (!Wd || !bd || !Wa || !ba || !div_term || !out) return S6D_EINVAL;
   if (pre && (((uintptr_t)Wd | (uintptr_t)Wa) & 15)) return S6D_EINVAL;
   const float *wd = reinterpret_cast<const float *>(Wd), *wa = reinterpret_cast<const float *>(Wa);
   if (pre && g_geo_form == 2) {
-    const unsigned grid = (unsigned)((NP + GEO_PAIRS - 1) / GEO_PAIRS);
     const u16 *wdh = reinterpret_cast<const u16 *>(Wd), *wah = reinterpret_cast<const u16 *>(Wa);
-    if (half) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&geo_embed2_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
-      hipLaunchKernelGGL((geo_embed2_kernel<true>), dim3(grid), dim3(GEO_THREADS), G2_LDS_BYTES, as_stream(stream), idx4, NP, wdh, bd, wah, ba, div_term, out);
-    } else {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&geo_embed2_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
-      hipLaunchKernelGGL((geo_embed2_kernel<false>), dim3(grid), dim3(GEO_THREADS), G2_LDS_BYTES, as_stream(stream), idx4, NP, wdh, bd, wah, ba, div_term, out);
-    }
+    if (half) geo_launch2_t<true>(src, wdh, bd, wah, ba, div_term, out, stream);
+    else geo_launch2_t<false>(src, wdh, bd, wah, ba, div_term, out, stream);
     return launch_status();
   }
   if (half) {
-    if (pre) geo_launch_t<true, true>(idx4, NP, wd, bd, wa, ba, div_term, out, stream);
-    else geo_launch_t<true, false>(idx4, NP, wd, bd, wa, ba, div_term, out, stream);
+    if (pre) geo_launch_t<true, true>(src, wd, bd, wa, ba, div_term, out, stream);
+    else geo_launch_t<true, false>(src, wd, bd, wa, ba, div_term, out, stream);
   } else {
-    if (pre) geo_launch_t<false, true>(idx4, NP, wd, bd, wa, ba, div_term, out, stream);
-    else geo_launch_t<false, false>(idx4, NP, wd, bd, wa, ba, div_term, out, stream);
+    if (pre) geo_launch_t<false, true>(src, wd, bd, wa, ba, div_term, out, stream);
+    else geo_launch_t<false, false>(src, wd, bd, wa, ba, div_term, out, stream);
   }
   return launch_status();
 }
 
+static int geo_from_idx(const float *idx4, long NP, const void *Wd, const float *bd, const void *Wa, const float *ba,
+                        const float *div_term, int C, int K, void *out, bool half, bool pre, void *stream) {
+  if (NP < 0) return S6D_EINVAL;
+  if (C != GEO_C || K != 3) return S6D_EUNSUPPORTED;      // released model: hidden_dim 256, angle_k 3
+  if (NP == 0) return S6D_OK;
+  if (!idx4) return S6D_EINVAL;
+  return geo_launch(GeoFromIdx{idx4, NP}, Wd, bd, Wa, ba, div_term, out, half, pre, stream);
+}
+
+// sizes of the points-fed entry points: S6D_OK with *empty set for B == 0 or N == 0
+static int geo_points_shape(int B, int N, bool *empty) {
+  *empty = B == 0 || N == 0;
+  if (B < 0 || N < 0) return S6D_EINVAL;
+  if (!*empty && (N < 4 || N > GEOIDX_MAX_N)) return S6D_EINVAL;
+  if (!*empty && (long)B * ((N + GEOIDX_ANCHORS - 1) / GEOIDX_ANCHORS) > 0x7fffffffL) return S6D_EINVAL;
+  return S6D_OK;
+}
+
+template <bool FULL>
+static int geo_indices_launch(const float *points, int B, int N, float sigma_d, float factor_a, float *idx4, int32_t *knn, void *stream) {
+  const int tiles = (N + GEOIDX_ANCHORS - 1) / GEOIDX_ANCHORS;
+  hipLaunchKernelGGL((geo_indices_kernel<FULL>), dim3((unsigned)(B * tiles)), dim3(GEOIDX_THREADS), 0, as_stream(stream), points, N, tiles,
+                     sigma_d, factor_a, idx4, knn);
+  return launch_status();
+}
+
+extern "C" int s6d_geo_knn_f32(const float *points, int B, int N, int32_t *knn, void *stream) {
+  bool empty;
+  const int rc = geo_points_shape(B, N, &empty);
+  if (rc != S6D_OK || empty) return rc;
+  if (!points || !knn) return S6D_EINVAL;
+  return geo_indices_launch<false>(points, B, N, 1.f, 1.f, nullptr, knn, stream);
+}
+
+extern "C" int s6d_geo_indices_f32(const float *points, int B, int N, float sigma_d, float factor_a, float *idx4, void *stream) {
+  bool empty;
+  const int rc = geo_points_shape(B, N, &empty);
+  if (rc != S6D_OK || empty) return rc;
+  if (!points || !idx4 || ((uintptr_t)idx4 & 15)) return S6D_EINVAL;
+  return geo_indices_launch<true>(points, B, N, sigma_d, factor_a, idx4, nullptr, stream);
+}
+
+static int geo_from_points(const float *points, int B, int N, float sigma_d, float factor_a, int32_t *knn, const void *Wd, const float *bd,
+                           const void *Wa, const float *ba, const float *div_term, int C, int K, void *out, bool half, bool pre,
+                           void *stream) {
+  bool empty;
+  int rc = geo_points_shape(B, N, &empty);
+  if (rc != S6D_OK) return rc;
+  if (C != GEO_C || K != 3) return S6D_EUNSUPPORTED;
+  if (empty) return S6D_OK;
+  if (!points || !knn || !Wd || !bd || !Wa || !ba || !div_term || !out) return S6D_EINVAL;      // before the first launch
+  if (pre && (((uintptr_t)Wd | (uintptr_t)Wa) & 15)) return S6D_EINVAL;
+  rc = geo_indices_launch<false>(points, B, N, sigma_d, factor_a, nullptr, knn, stream);
+  if (rc != S6D_OK) return rc;
+  return geo_launch(GeoFromPoints{points, knn, (long)B * N * N, N, sigma_d, factor_a}, Wd, bd, Wa, ba, div_term, out, half, pre, stream);
+}
+
 extern "C" int s6d_geo_embedding_f32(const float *idx4, long NP, const float *Wd, const float *bd, const float *Wa,
                                      const float *ba, const float *div_term, int C, int K, float *out, void *stream) {
-  return geo_launch(idx4, NP, Wd, bd, Wa, ba, div_term, C, K, out, false, false, stream);
+  return geo_from_idx(idx4, NP, Wd, bd, Wa, ba, div_term, C, K, out, false, false, stream);
 }
 
 extern "C" int s6d_geo_embedding_f16(const float *idx4, long NP, const float *Wd, const float *bd, const float *Wa,
                                      const float *ba, const float *div_term, int C, int K, void *out_f16, void *stream) {
-  return geo_launch(idx4, NP, Wd, bd, Wa, ba, div_term, C, K, out_f16, true, false, stream);
+  return geo_from_idx(idx4, NP, Wd, bd, Wa, ba, div_term, C, K, out_f16, true, false, stream);
 }
 
 extern "C" int s6d_geo_embedding_split(const float *idx4, long NP, const void *Wd_hilo, const float *bd, const void *Wa_hilo,
                                        const float *ba, const float *div_term, int C, int K, void *out, int out_f16, void *stream) {
-  return geo_launch(idx4, NP, Wd_hilo, bd, Wa_hilo, ba, div_term, C, K, out, out_f16 != 0, true, stream);
+  return geo_from_idx(idx4, NP, Wd_hilo, bd, Wa_hilo, ba, div_term, C, K, out, out_f16 != 0, true, stream);
+}
+
+extern "C" int s6d_geo_embedding_points_f32(const float *points, int B, int N, float sigma_d, float factor_a, int32_t *knn, const float *Wd,
+                                            const float *bd, const float *Wa, const float *ba, const float *div_term, int C, int K,
+                                            float *out, void *stream) {
+  return geo_from_points(points, B, N, sigma_d, factor_a, knn, Wd, bd, Wa, ba, div_term, C, K, out, false, false, stream);
+}
+
+extern "C" int s6d_geo_embedding_points_f16(const float *points, int B, int N, float sigma_d, float factor_a, int32_t *knn, const float *Wd,
+                                            const float *bd, const float *Wa, const float *ba, const float *div_term, int C, int K,
+                                            void *out_f16, void *stream) {
+  return geo_from_points(points, B, N, sigma_d, factor_a, knn, Wd, bd, Wa, ba, div_term, C, K, out_f16, true, false, stream);
+}
+
+extern "C" int s6d_geo_embedding_points_split(const float *points, int B, int N, float sigma_d, float factor_a, int32_t *knn,
+                                              const void *Wd_hilo, const float *bd, const void *Wa_hilo, const float *ba,
+                                              const float *div_term, int C, int K, void *out, int out_f16, void *stream) {
+  return geo_from_points(points, B, N, sigma_d, factor_a, knn, Wd_hilo, bd, Wa_hilo, ba, div_term, C, K, out, out_f16 != 0, true, stream);
 }

@@ -1111,6 +1111,57 @@ def geo_embedding(idx4, Wd, bd, Wa, ba, div_term, out_dtype=torch.float32, split
     return out
 
 
+GEO_POINTS_MAX_N = 256          # clouds the points-fed geometric kernels serve (include/sam6d_hip.h: s6d_geo_indices_f32), 4 <= N
+
+
+def geo_knn(points):
+    """points (B,N,3) f32 -> (B,N,3) i32: the three nearest neighbours of every point besides itself, nearest first, ties to the
+    lower index (the neighbour table of the points-fed geometric embedding)."""
+    _chk(points, torch.float32, "points", 3)
+    if points.shape[-1] != 3:
+        raise RuntimeError("points must be (B,N,3)")
+    B, N, _ = points.shape
+    knn = torch.empty(B, N, 3, dtype=torch.int32, device=points.device)
+    _call("s6d_geo_knn_f32", _ptr(points), B, N, _ptr(knn), _stream())
+    return knn
+
+
+def geo_indices(points, sigma_d, factor_a):
+    """points (B,N,3) f32 -> idx4 (B,N,N,4) f32 = [d_idx, a_idx x3] of every pair: get_embedding_indices (transformer.py:303-332) in
+    one launch, distances by direct differences (the diagonal is exactly 0), neighbour ties to the lower index."""
+    _chk(points, torch.float32, "points", 3)
+    if points.shape[-1] != 3:
+        raise RuntimeError("points must be (B,N,3)")
+    B, N, _ = points.shape
+    idx4 = torch.empty(B, N, N, 4, dtype=torch.float32, device=points.device)
+    _call("s6d_geo_indices_f32", _ptr(points), B, N, float(sigma_d), float(factor_a), _ptr(idx4), _stream())
+    return idx4
+
+
+def geo_embedding_points(points, sigma_d, factor_a, Wd, bd, Wa, ba, div_term, out_dtype=torch.float32, split=None):
+    """points (B,N,3) f32 -> (B,N,N,256): geo_embedding(geo_indices(points, ...), ...) bit for bit without the idx4 tensor -- the
+    embedding kernels compute the four indices of a pair in their prologue; the only temporary is the (B,N,3) neighbour table."""
+    for a, nm in ((points, "points"), (Wd, "Wd"), (bd, "bd"), (Wa, "Wa"), (ba, "ba"), (div_term, "div_term")):
+        _chk(a, torch.float32, nm)
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise RuntimeError("points must be (B,N,3)")
+    if out_dtype not in (torch.float32, torch.float16):
+        raise RuntimeError("the embedding is stored in float32 or float16")
+    B, N, _ = points.shape
+    knn = torch.empty(B, N, 3, dtype=torch.int32, device=points.device)
+    out = torch.empty(B, N, N, Wd.shape[0], dtype=out_dtype, device=points.device)
+    head = (_ptr(points), B, N, float(sigma_d), float(factor_a), _ptr(knn))
+    if split is not None and have("geo_embedding_points"):
+        for a, nm in ((split[0], "Wd_hilo"), (split[1], "Wa_hilo")):
+            _chk(a, torch.bfloat16, nm, 3)
+        _call("s6d_geo_embedding_points_split", *head, _ptr(split[0]), _ptr(bd), _ptr(split[1]), _ptr(ba), _ptr(div_term), Wd.shape[0], 3,
+              _ptr(out), 1 if out_dtype == torch.float16 else 0, _stream())
+        return out
+    _call("s6d_geo_embedding_points_f32" if out_dtype == torch.float32 else "s6d_geo_embedding_points_f16", *head, _ptr(Wd), _ptr(bd),
+          _ptr(Wa), _ptr(ba), _ptr(div_term), Wd.shape[0], 3, _ptr(out), _stream())
+    return out
+
+
 def fine_assign(atten, pts2):
     """atten (B,M1,M2) f32, pts2 (B,M2-1,3) f32 -> pred (B,M1-1,3), wsum (B,M1-1), w1 (B,M1-1)."""
     _chk(atten, torch.float32, "atten", 3)
@@ -1304,7 +1355,7 @@ _FUSED = {}
 
 def have(name):
     if name not in _FUSED:
-        sym = {"rpe_attention": "s6d_rpe_attention_f32", "rpe_attention_packed": "s6d_rpe_attention_packed_f32", "geo_embedding": "s6d_geo_embedding_f32", "geo_embedding_f16": "s6d_geo_embedding_f16", "geo_embedding_split": "s6d_geo_embedding_split",
+        sym = {"rpe_attention": "s6d_rpe_attention_f32", "rpe_attention_packed": "s6d_rpe_attention_packed_f32", "geo_embedding": "s6d_geo_embedding_f32", "geo_embedding_f16": "s6d_geo_embedding_f16", "geo_embedding_split": "s6d_geo_embedding_split", "geo_indices": "s6d_geo_indices_f32", "geo_embedding_points": "s6d_geo_embedding_points_split",
                "fine_assign": "s6d_fine_assign_f32", "fine_match": "s6d_fine_match_f32", "pem_pre": "s6d_pem_compact_cloud_f32", "coarse_sample": "s6d_coarse_sample_f32", "upsample_gather": "s6d_upsample_gather_f32",
                "min_dist": "s6d_min_dist_f32", "rot_from_h": "s6d_rot_from_h_f32", "weighted_procrustes": "s6d_weighted_procrustes_f32", "add_layernorm": "s6d_add_layernorm_bf16", "gemm_bf16": "s6d_gemm_bf16", "gemm_bf16_res": "s6d_gemm_bf16_res", "gemm_bf16_lnfold": "s6d_gemm_bf16_lnfold", "gemm_f16": "s6d_gemm_f16", "gemm_fp8": "s6d_gemm_fp8", "layernorm_fp8": "s6d_layernorm_fp8", "layernorm_f32out": "s6d_layernorm_bf16_f32", "linear_f32": "s6d_linear_f32", "attn_output_chain": "s6d_attn_output_chain_f32", "win_attention": "s6d_win_attention_layout_bf16",
                "pairwise_cosine": "s6d_pairwise_cosine_f32",

@@ -417,14 +417,23 @@ class GeometricStructureEmbedding(nn.Module):
     def forward(self, points):
         if policy.guard("pem.GeometricStructureEmbedding", cuda=points.is_cuda, have=ops.have("geo_embedding"), angle_k3=self.angle_k == 3,
                         C256=self.proj_d.weight.shape[0] == 256):
-            d_idx, a_idx = self.get_embedding_indices(points)
-            idx4 = torch.cat([d_idx.unsqueeze(-1), a_idx], dim=-1).contiguous()          # (B,N,N,4)
             # S6D_PEM_GEO_DTYPE=fp16: the embedding is STORED in IEEE half (same arithmetic up to the store); its twelve readers
             # (rpe_attention_kernel, bound by streaming it) then move half the bytes.  Measured margins: DESIGN.md 4.
             half = policy.current().pem_geo_dtype == "fp16" and ops.have("geo_embedding_f16")
-            return ops.geo_embedding(idx4, self.proj_d.weight.contiguous(), self.proj_d.bias, self.proj_a.weight.contiguous(),
-                                     self.proj_a.bias, self.embedding.div_term.contiguous(),
-                                     out_dtype=torch.float16 if half else torch.float32, split=self._split_weights())
+            weights = (self.proj_d.weight.contiguous(), self.proj_d.bias, self.proj_a.weight.contiguous(), self.proj_a.bias,
+                       self.embedding.div_term.contiguous())
+            kw = dict(out_dtype=torch.float16 if half else torch.float32, split=self._split_weights())
+            # S6D_GEO_FROM_POINTS=1 (default): the index stage runs inside the kernels (pair distances by direct differences, neighbour
+            # ties to the lower index) -- no idx4, no (B,N,N,3,3) temporaries, no library launches; "0": the statements below
+            # Clouds outside what those kernels serve (N, dtype) keep the path through idx4 as before, strict mode included: a plain `if`,
+            # not a guard -- only a library without the entry points is a recorded fall-back.
+            served = points.dtype == torch.float32 and points.dim() == 3 and 4 <= points.shape[1] <= ops.GEO_POINTS_MAX_N
+            if policy.current().geo_from_points == "1" and served and policy.guard(
+                    "pem.GeometricStructureEmbedding.from_points", cuda=points.is_cuda, have=ops.have("geo_embedding_points")):
+                return ops.geo_embedding_points(points.contiguous(), self.sigma_d, self.factor_a, *weights, **kw)
+            d_idx, a_idx = self.get_embedding_indices(points)
+            idx4 = torch.cat([d_idx.unsqueeze(-1), a_idx], dim=-1).contiguous()          # (B,N,N,4)
+            return ops.geo_embedding(idx4, *weights, **kw)
         outs = []
         for p in points.split(4, dim=0):     # bound the (b,N,N,k,256) intermediate of the library path
             d_idx, a_idx = self.get_embedding_indices(p)

@@ -40,6 +40,7 @@ _ENV = {   # field: (variable, default, type)
     "pem_pre": ("S6D_PEM_PRE", "", str),                         # "library": torch pre-processing
     "rpe_fold": ("S6D_RPE_FOLD", "1", str),
     "geo_presplit": ("S6D_GEO_PRESPLIT", "1", str),
+    "geo_from_points": ("S6D_GEO_FROM_POINTS", "1", str),        # geometric embedding straight from the points; "0": through the idx4 tensor
     "desc_group": ("S6D_DESC_GROUP", "1", str),                  # descriptors of a frame group in one DINOv2 pass
     "gemm_res": ("S6D_GEMM_RES", "0", str),
     "lnfold": ("S6D_LNFOLD", "1", str),
@@ -71,6 +72,7 @@ class PrecisionPolicy:
     pem_pre: str = ""
     rpe_fold: str = "1"
     geo_presplit: str = "1"
+    geo_from_points: str = "1"
     desc_group: str = "1"
     gemm_res: str = "0"
     lnfold: str = "1"

@@ -39,6 +39,7 @@ bf16 products = 0.56 of the nominal figure, at ≈ 1.7 – 2.0 GHz under the pow
 | `plin_kernel` (s6d_plin) | a15, a16, a20, a21 | HBM (3-term bf16 MFMA inside) | x, residual read once, y written once: 201 MB at M = 65536 | {plin['avg_ms']*1e3:.1f} µs at M = 65536 (the q / k / v and plain projections: 60 launches per step) | {plin['frac']:.2f} of HBM |
 | `pchain_kernel<2 / 1>` (s6d_pchain, **round 6**) | a15, a16, a20, a21 | MFMA 3-term bf16 | Linear + residual + LN + FFN 256 → 512 → 256 + residual + LN: attention output and residual read once, y written once (201 MB at M = 65536; h and the 512-wide activations stay on chip); 155 GFLOP executed | {pch['avg_ms']*1e3:.0f} µs at M = 65536 (6 + 24 smaller in 32-row workgroups) | {pch['frac']:.3f} executed ({pch['hbm_gbps']/1e3:.2f} TB/s) |
 | `geo_embed_kernel` (s6d_geo) | a14 | MFMA 3-term bf16 | 650 GFLOP fp32 as written; writes 1.27 GB | {geo['avg_ms']:.2f} ms (2) | {geo['frac']:.3f}; the bare product stream of this kernel: 1.41 of 1.90 ms (`profiles/r06_geo_embed.md`) |
+| `geo_indices_kernel` (s6d_geo) | a14, index stage (`transformer.py:303-332`) | fp32 VALU, cloud in LDS, wave-wide 3-NN selection | points → `knn (B,N,3)` in front of the points-fed `geo_embed_kernel` prologue (or → `idx4` standalone); replaces the library chain matmul / topk / gather / cross / norm / atan2 / cat and its `(B,N,N,3,3)` temporaries | `profiles/geo_from_points.md` | — (O(B·N) output; not a roofline kernel) |
 | `rpe_attention_kernel<4,true>` (s6d_rpe) | a15 | HBM | 1.27 GB embedding stream | {rpe['avg_ms']:.3f} ms (12) | {rpe['frac']:.3f} |
 | `pe_group_mlp_kernel` (s6d_pe) | a19 | MFMA 3-term bf16 | 43.7 / 87.3 GFLOP as written (ns = 32 / 64) | 0.24 / 0.36 ms (2 + 2) | 0.22 / 0.30 executed |
 | `fine_split + 3 × fine_sweep_kernel` (s6d_fine) | a22–a23 | MFMA 3-term | 618 GFLOP executed; 4.2 MB / instance | {fine['avg_ms']:.3f} ms (1) | {fine['frac']:.3f} |

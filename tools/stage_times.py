@@ -1,10 +1,16 @@
-"""Per-stage wall times of the MI355X PEM path (diagnostic; run on the GPU box)."""
+"""Per-stage wall times of the MI355X PEM path (diagnostic; run on the GPU box):
+python tools/stage_times.py [B]
+python tools/stage_times.py --geo-ab [result.json]   the geo_embedding stage alone, policy field geo_from_points "0" / "1" alternating
+                                                     in this process at 32 and 10 instances (quoted in profiles/geo_from_points.md)"""
+import json
+import statistics
 import sys
 import time
 
 import torch
 
 sys.path.insert(0, ".")
+from sam6d_amd import policy  # noqa: E402
 from sam6d_amd.pem import pose_estimation_model as pm  # noqa: E402
 from sam6d_amd.utils import seeded, synth  # noqa: E402
 
@@ -43,5 +49,75 @@ def main(B=32):
     print("max mem GB", torch.cuda.max_memory_allocated() / 2**30)
 
 
+def _event_ms(fn, calls):
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def _launches(fn):
+    """Device kernels of one call, by name (torch.profiler, a pass of its own)."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    names = {}
+    for ev in prof.events():
+        if str(getattr(ev, "device_type", "")).endswith("CUDA") and "memcpy" not in ev.name.lower() and "memset" not in ev.name.lower():
+            names[ev.name] = names.get(ev.name, 0) + 1
+    return names
+
+
+def geo_ab(path=None, rounds=7, calls=20):
+    """net.geo_embedding on the 197-token cloud from the points ("1") against the path through the idx4 tensor ("0"): device-event
+    times of alternating rounds, the largest difference of the two embeddings, the device launches of one call of either path."""
+    net = seeded.load_seeded(pm.Net(pm.default_cfg()).eval(), 1).cuda()
+    geo = net.geo_embedding
+    out = {"rounds": rounds, "calls_per_round": calls, "device": torch.cuda.get_device_name(0)}
+    with torch.no_grad():
+        for B in (32, 10):
+            g = torch.Generator().manual_seed(B)
+            pts = torch.randn(B, 197, 3, generator=g) * 0.5
+            pts[:, 0] = 100.0
+            pts = pts.cuda()
+            rows = {"0": [], "1": []}
+            for _ in range(rounds):
+                for mode in ("0", "1"):
+                    with policy.use(geo_from_points=mode):
+                        rows[mode].append(round(_event_ms(lambda: geo(pts), calls), 4))
+            with policy.use(geo_from_points="0"):
+                a = geo(pts)
+            with policy.use(geo_from_points="1"):
+                b = geo(pts)
+            off = ~torch.eye(197, dtype=torch.bool, device="cuda").expand(B, 197, 197)
+            d = (a - b).abs()
+            r = {"idx4_path_ms": rows["0"], "from_points_ms": rows["1"], "idx4_path_median_ms": statistics.median(rows["0"]),
+                 "from_points_median_ms": statistics.median(rows["1"]), "max_abs_diff_off_diagonal": d[off].max().item(),
+                 "max_abs_diff_diagonal": d[~off].max().item(), "mean_abs_diff": d.mean().item()}
+            print(B, r, flush=True)
+            for mode, key in (("0", "idx4_path_launches"), ("1", "from_points_launches")):
+                with policy.use(geo_from_points=mode):
+                    names = _launches(lambda: geo(pts))
+                r[key] = {"total": sum(names.values()), "library": sum(v for k, v in names.items() if "s6d" not in k), "by_name": names}
+                print(B, key, r[key]["total"], "library:", r[key]["library"], flush=True)
+            out[f"B{B}"] = r
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+    else:
+        print(json.dumps(out))
+
+
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 32)
+    if len(sys.argv) > 1 and sys.argv[1] == "--geo-ab":
+        geo_ab(sys.argv[2] if len(sys.argv) > 2 else None)
+    else:
+        main(int(sys.argv[1]) if len(sys.argv) > 1 else 32)
