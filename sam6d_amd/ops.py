@@ -210,6 +210,10 @@ def _rows3(t, name):
     return t, C
 
 
+ATTN_ROWS_MAX_KEYS = 1024      # keys the rows kernel serves (csrc/s6d_rpe.hip: a workgroup's 4 waves x 4 heads x 4 B of scores per key, rounded
+#                                up to four keys, in 64 KiB of LDS); beyond it s6d_rpe_attention_* / s6d_mha_* return S6D_EUNSUPPORTED
+
+
 def rpe_attention(q, k, v, qt, qb, embed, scale):
     """q,k,v (B,N,256) (column blocks of one projection output are taken as they are); qt (B,4,N,256); qb (B,4,N);
     embed (B,N,N,256) -> (B,N,256), all f32."""

@@ -122,7 +122,9 @@ class MultiHeadAttention(nn.Module):
         self.scale = 1.0 / math.sqrt(d_model // num_heads)
 
     def forward(self, xq, xk, xv):
-        if policy.guard("pem.MultiHeadAttention", cuda=xq.is_cuda, have=ops.have("mha"), C256=xq.shape[-1] == 256):
+        # (keys: the rows kernel holds a query row's scores in LDS; a longer memory takes the library statements)
+        if policy.guard("pem.MultiHeadAttention", cuda=xq.is_cuda, have=ops.have("mha"), C256=xq.shape[-1] == 256,
+                        keys=xk.shape[1] <= ops.ATTN_ROWS_MAX_KEYS):
             C = xq.shape[-1]
             q = plinear(self, self.proj_q, xq)
             if xk is xv:                                              # k | v of the memory in one launch
@@ -177,7 +179,7 @@ class RPEMultiHeadAttention(nn.Module):
         B, N, C = x.shape
         if policy.guard("pem.RPEMultiHeadAttention", cuda=x.is_cuda, have=ops.have("rpe_attention_packed") and ops.have("linear_f32"),
                         f32=x.dtype == torch.float32, C256=C == 256, no_grad=not torch.is_grad_enabled(),
-                        rpe_fold=policy.current().rpe_fold == "1"):
+                        keys=N <= ops.ATTN_ROWS_MAX_KEYS, rpe_fold=policy.current().rpe_fold == "1"):
             # q | k | v | q~ | qb from ONE launch of the projection kernel; the attention core reads them in place
             proj = plinear(self, (self.proj_q, self.proj_k, self.proj_v, self._fold()), x)
             return ops.rpe_attention_packed(proj, embed, self.scale)
@@ -188,7 +190,7 @@ class RPEMultiHeadAttention(nn.Module):
         qh = _split(q)
         qt = torch.einsum("bhnc,hcj->bhnj", qh, self.proj_p.weight.view(HEADS, c, C))
         qb = torch.einsum("bhnc,hc->bhn", qh, self.proj_p.bias.view(HEADS, c))
-        if ops.have("rpe_attention") and x.is_cuda:
+        if policy.guard("pem.RPEMultiHeadAttention.core", cuda=x.is_cuda, have=ops.have("rpe_attention"), keys=N <= ops.ATTN_ROWS_MAX_KEYS):
             return ops.rpe_attention(q, k, v, qt, qb, embed, self.scale)
         sp = torch.einsum("bhnj,bnmj->bhnm", qt, embed.float()) + qb.unsqueeze(-1)
         a = torch.softmax((qh @ _split(k).transpose(-1, -2) + sp) * self.scale, dim=-1)

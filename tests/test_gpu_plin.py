@@ -92,9 +92,17 @@ def test_linear_attention_vs_the_library_statement(B, I, J):
         return t / t.norm(dim=-1, keepdim=True) * n
 
     kf = ops.linear_attn_focus(kvp[..., :256].contiguous(), inv, 3)
-    out = ops.linear_attention(xq, inv, 3, kf, kvp[..., 256:])
-    sentinel = torch.full((B, I + 1, 256), 7.0).cuda()                # nothing is written past row I of a batch element
-    assert out.shape == (B, I, 256) and torch.isfinite(out).all() and sentinel[0, I, 0] == 7.0
+    # the entry point writes into a buffer of this test's own: B I rows and 64 more that hold a sentinel, as does the tail of the
+    # workspace -- nothing is written past row I of the last batch element (the last 64-row block is ragged) or behind the workspace
+    buf = torch.full((B * I + 64, 256), 7.0).cuda()
+    nws = ops._size("s6d_linear_attention_workspace_floats", B)
+    ws = torch.full((nws + 64,), 7.0).cuda()
+    v = kvp[..., 256:]
+    ops._call("s6d_linear_attention_f32", xq.data_ptr(), inv.data_ptr(), 3, kf.data_ptr(), kf.stride(1), v.data_ptr(), v.stride(1), B, I, J,
+              256, ws.data_ptr(), buf.data_ptr(), ops._stream())
+    out = buf[:B * I].view(B, I, 256)
+    assert torch.isfinite(out).all() and bool((buf[B * I:] == 7.0).all()) and bool((ws[nws:] == 7.0).all())
+    assert torch.equal(ops.linear_attention(xq, inv, 3, kf, v), out)
 
     def split(t):
         return t.view(t.shape[0], t.shape[1], 4, 64).transpose(1, 2)
