@@ -69,7 +69,6 @@ def _build_locked(force, verbose, objdir):
     extra = os.environ.get("S6D_EXTRA_HIPCC_FLAGS", "").split()
     cflags = [f for f in FLAGS if f != "-shared"] + extra
     hdrs = glob.glob(os.path.join(_CSRC, "*.h")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h"))
-    # s6d_attn_f16.hip re-compiles s6d_attn.hip under another element type: it depends on that source too
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     tag = os.path.join(objdir, ".flags")
     flags_now = " ".join(cflags)
@@ -78,7 +77,7 @@ def _build_locked(force, verbose, objdir):
 
     def one(src):
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
-        dep_t = max(hdr_t, os.path.getmtime(src), max(os.path.getmtime(x) for x in sources()) if src.endswith("_f16.hip") else 0)
+        dep_t = max(hdr_t, os.path.getmtime(src))
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < dep_t:
             cmd = [HIPCC] + cflags + file_flags(src) + ["-c", src, "-o", obj]
             if verbose:

@@ -5,6 +5,14 @@
 
 #include "../../include/sam6d_hip.h"
 
+// A place that relies on a wave's LDS operations executing in program order (nothing to do on the GPU).  On the tests' host emulator
+// (tests/hipemu.py, HIPEMU) the lanes of a wave are independent fibers and the place is a real rendezvous of the wave.
+#ifdef HIPEMU
+#define S6D_WAVE_RENDEZVOUS() hipemu::wave_barrier()
+#else
+#define S6D_WAVE_RENDEZVOUS() do { } while (0)
+#endif
+
 namespace s6d {
 
 constexpr int kWave = 64;

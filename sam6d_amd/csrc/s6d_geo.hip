@@ -192,7 +192,7 @@ constexpr int GEO_C = 256;          // hidden dim
 constexpr int GEO_ROW = 40;         // LDS row stride (bf16): 32 channels + 8 pad (80 B = 5 chunks of 16 B)
 // A ds_read_b128 lane group is {rows 0-3,12-15 reading chunk g} + {rows 4-11 reading chunk g + 1}: with any odd row stride these
 // meet on 3 of 16 bank slots (2-way conflict on every fragment read: SQ_LDS_BANK_CONFLICT was a quarter of the kernel's cycles).
-// Rows with (row >> 2 ^ row >> 3) & 1 therefore keep their chunks pairwise swapped (same fix as csrc/s6d_attn.hip S6D_GLB_KSWZ).
+// Rows with (row >> 2 ^ row >> 3) & 1 therefore keep their chunks pairwise swapped (same fix as kswz() in csrc/s6d_attn_common.h).
 #ifndef S6D_GEO_KSWZ
 #define S6D_GEO_KSWZ 1
 #endif

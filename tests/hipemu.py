@@ -38,15 +38,9 @@ def build(force=False, files=None):
         if files is not None and os.path.basename(f) not in files:
             continue
         text = open(f).read()
-        if os.path.basename(f) == "s6d_attn_f16.hip":
-            # the IEEE-half build of the attention kernels = s6d_attn.hip under S6D_ATTN_F16: include the TEXT (the transformations
-            # below must reach it) instead of the #include
-            text = "#define S6D_ATTN_F16 1\n" + open(os.path.join(CSRC, "s6d_attn.hip")).read()
-        # dynamic LDS: `extern __shared__ ... char name[];` refers to a global array defined below
+        # dynamic LDS: `extern __shared__ ... char name[];` refers to a global array defined below (headers that hold kernels,
+        # csrc/s6d_attn_*.h, declare it through a macro keyed on HIPEMU: only .hip text is rewritten here)
         text = text.replace("extern __shared__", "extern")
-        # places that rely on a wave executing in lockstep are marked with a comment in the product source; lanes are
-        # independent fibers here, so the marker becomes a real rendezvous of the wave
-        text = re.sub(r"^[ \t]*// hipemu: wave rendezvous[^\n]*$", "hipemu::wave_barrier();", text, flags=re.M)
         dst = os.path.join(OUT, os.path.basename(f)[:-4] + ".cc")
         with open(dst, "w") as g:
             g.write(f'#line 1 "{f}"\n' + text)

@@ -133,6 +133,30 @@ def test_float16_kernels_on_the_emulator(emu):
     T.test_add_layernorm_float16()
 
 
+@pytest.mark.parametrize("B,N,nh", [(2, 50, 2), (1, 65, 1)])
+def test_float16_seq_attention_head_dim_80_on_the_emulator(emu, B, N, nh):
+    T.test_seq_attention_float16_head_dim_80_vs_float64(B, N, nh)
+
+
+def test_float16_seq_attention_head_major_on_the_emulator(emu):
+    T.test_seq_attention_float16_head_major_equals_token_major()
+
+
+def test_kernel_sources_use_the_emulator_macros():
+    """A wave rendezvous is S6D_WAVE_RENDEZVOUS() (csrc/s6d_common.h) in every source: the old `// hipemu: wave rendezvous` comment is
+    transformed by nothing any more and would silently be no barrier.  tests/hipemu.py rewrites `extern __shared__` in .hip text only,
+    so a header that holds kernels declares its dynamic LDS through S6D_ATTN_DYN_LDS(), never bare."""
+    import glob
+    import os
+    import re
+
+    from tests import hipemu
+    for f in glob.glob(os.path.join(hipemu.CSRC, "*.h")) + glob.glob(os.path.join(hipemu.CSRC, "*.hip")):
+        text = open(f).read()
+        assert "hipemu: wave rendezvous" not in text, f
+        assert not (f.endswith(".h") and re.search(r"^\s*extern __shared__", text, flags=re.M)), f
+
+
 def test_pem_vit_fused_half_pipeline_on_the_emulator(emu):
     """The PEM ViT (feature_extraction.ViT) through its fused IEEE-half pipeline (s6d_gemm_f16, s6d_seq_attention_f16,
     s6d_add_layernorm_f16) against its own fp32 module path: taps within 2e-3 relative (half's 2^-11 per stored activation), and

@@ -174,6 +174,35 @@ def test_seq_attention_float16_vs_torch(B=2, N=197, nh=12, hd=64):
     assert (out.float().cpu() - ref).abs().max() < 4e-3          # P is rounded to half (2^-11) before the PV product
 
 
+@pytest.mark.parametrize("B,N,nh", [(2, 50, 2), (1, 65, 1)])
+def test_seq_attention_float16_head_dim_80_vs_float64(B, N, nh, hd=80):
+    """attn_window_kernel<80, 8, false> of the IEEE-half unit (s6d_seq_attention_f16; the ViT-B shape above is head dim 64): 50 keys
+    are less than one 64-key tile, 65 are one full tile plus one ragged key.  Same bound as above (P is rounded to half before the
+    PV product), against the float64 statement on the same half operands."""
+    from sam6d_amd import ops
+    g = torch.Generator().manual_seed(N + nh)
+    qkv = torch.randn(B, N, 3 * nh * hd, generator=g).to(torch.float16).cuda()
+    out = ops.seq_attention(qkv, nh, hd ** -0.5)
+    assert out.dtype == torch.float16
+    q, k, v = qkv.double().cpu().view(B, N, 3, nh, hd).permute(2, 0, 3, 1, 4).unbind(0)
+    ref = (torch.softmax(q @ k.transpose(-1, -2) * hd ** -0.5, -1) @ v).transpose(1, 2).reshape(B, N, nh * hd)
+    err = (out.double().cpu() - ref).abs().max().item()
+    print(f"half seq attention B={B} N={N} nh={nh} hd={hd}: max abs err {err:.3e}")
+    assert err < 4e-3
+
+
+def test_seq_attention_float16_head_major_equals_token_major(B=1, N=65, nh=2, hd=64):
+    """s6d_seq_attention_strided_f16 on the head-major operand ((3 nh, B N, hd)) gives bit for bit what the token-major call gives:
+    only addresses differ (the bf16 twin is the last assertion of test_seq_attention_vs_torch)."""
+    from sam6d_amd import ops
+    g = torch.Generator().manual_seed(N + nh + hd)
+    qkv = torch.randn(B, N, 3 * nh * hd, generator=g).to(torch.float16).cuda()
+    tok = ops.seq_attention(qkv, nh, hd ** -0.5)
+    hm = qkv.view(B * N, 3 * nh, hd).transpose(0, 1).contiguous()
+    out = ops.seq_attention(hm, nh, hd ** -0.5, seq_len=N)
+    assert out.dtype == torch.float16 and torch.equal(out, tok)
+
+
 def test_add_layernorm_float16():
     from sam6d_amd import ops
     g = torch.Generator().manual_seed(3)

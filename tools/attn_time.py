@@ -1,4 +1,5 @@
-"""Time the SAM encoder's attention launches per build variant of csrc/s6d_attn.hip (tools/attn_variants.sh), all in ONE process so
+"""Time the SAM encoder's attention launches per build variant of csrc/s6d_attn.hip and the csrc/s6d_attn_*.h family headers it
+includes (tools/attn_variants.sh), all in ONE process so
 that the comparison is free of box-to-box clock variance: global attention over the 64 x 64 grid (B frames x 16 heads x 80) and
 the 14 x 14 windowed attention, against the base build's output (layout / schedule variants must reproduce it bit for bit; the
 ablation builds are timing probes and are not compared).

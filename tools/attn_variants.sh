@@ -1,5 +1,6 @@
 #!/bin/bash
-# Stand-alone builds of the attention kernels with the profiling / layout switches of csrc/s6d_attn.hip (header of that file) for
+# Stand-alone builds of the attention kernels (csrc/s6d_attn.hip = the bf16 unit over csrc/s6d_attn_{common,seq,win16,global}.h) with
+# the profiling / layout switches those headers keep, each described where it is defined, for
 # tools/attn_time.py:   tools/attn_variants/libattn_<name>.so   (git-ignored; travels with the gpurun snapshot)
 set -e
 cd "$(dirname "$0")/.."

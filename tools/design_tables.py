@@ -34,8 +34,8 @@ bf16 products = 0.56 of the nominal figure, at ≈ 1.7 – 2.0 GHz under the pow
 | `<3,true>` qkv, norm1 folded | a4 | MFMA | 644 GFLOP | {qkv['avg_ms']:.3f} ms (64) | {qkv['frac']:.3f} |
 | `<2,true>` proj / lin2 + residual + row statistics | a4, a5 | MFMA | 215 / 859 GFLOP | {proj['avg_ms']:.3f} / {lin2['avg_ms']:.3f} ms (64 each) | {proj['frac']:.3f} / {lin2['frac']:.3f} |
 | `gemm4_bf16_kernel` (s6d_gemm4, round 6): the four-wave form, 128 × 128 wave tiles | a4, a5 | MFMA | same shapes, same bits | selectable (`s6d_set_gemm_wave_tile(128)`): +0.5 … +4.6 % per kernel alone, −0.3 … −0.65 % in the step (`profiles/r06_gemm4.md`) | — |
-| `attn_global64_kernel<80,8,3>` (s6d_attn) | a4 (4 blocks) | MFMA | 4·4096²·80·16 heads·16 frames = 1374 GFLOP; 671 MB | {glb['avg_ms']:.3f} ms (8) | {glb['frac']:.3f} |
-| `attn_window16p_kernel<80,true>` | a3–a4 (28 blocks) | HBM | 671 MB (78.6 GFLOP) | {win['avg_ms']:.3f} ms (56) | {win['frac']:.3f} of HBM |
+| `attn_global64_kernel<80,8,3>` (s6d_attn_global.h; unit s6d_attn) | a4 (4 blocks) | MFMA | 4·4096²·80·16 heads·16 frames = 1374 GFLOP; 671 MB | {glb['avg_ms']:.3f} ms (8) | {glb['frac']:.3f} |
+| `attn_window16p_kernel<80,true>` (s6d_attn_win16.h) | a3–a4 (28 blocks) | HBM | 671 MB (78.6 GFLOP) | {win['avg_ms']:.3f} ms (56) | {win['frac']:.3f} of HBM |
 | `plin_kernel` (s6d_plin) | a15, a16, a20, a21 | HBM (3-term bf16 MFMA inside) | x, residual read once, y written once: 201 MB at M = 65536 | {plin['avg_ms']*1e3:.1f} µs at M = 65536 (the q / k / v and plain projections: 60 launches per step) | {plin['frac']:.2f} of HBM |
 | `pchain_kernel<2 / 1>` (s6d_pchain, **round 6**) | a15, a16, a20, a21 | MFMA 3-term bf16 | Linear + residual + LN + FFN 256 → 512 → 256 + residual + LN: attention output and residual read once, y written once (201 MB at M = 65536; h and the 512-wide activations stay on chip); 155 GFLOP executed | {pch['avg_ms']*1e3:.0f} µs at M = 65536 (6 + 24 smaller in 32-row workgroups) | {pch['frac']:.3f} executed ({pch['hbm_gbps']/1e3:.2f} TB/s) |
 | `geo_embed_kernel` (s6d_geo) | a14 | MFMA 3-term bf16 | 650 GFLOP fp32 as written; writes 1.27 GB | {geo['avg_ms']:.2f} ms (2) | {geo['frac']:.3f}; the bare product stream of this kernel: 1.41 of 1.90 ms (`profiles/r06_geo_embed.md`) |

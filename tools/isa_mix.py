@@ -2,7 +2,10 @@
 VMEM / SALU / wait instructions a loop iteration issues (no GPU needed).  With the issue-rate figures of
 tools/probes/valu_rate.hip this gives a lower bound for a wave's time per iteration and shows which class dominates.
 
-    python tools/isa_mix.py s6d_attn.hip 'attn_global_kernel<80, 4, 1>'
+    python tools/isa_mix.py s6d_attn.hip 'attn_global64_kernel<80, 8, 3>'
+
+The first argument is a compiled unit (csrc/*.hip): a kernel that lives in a header (the attention families, csrc/s6d_attn_*.h) is
+looked up in the unit that instantiates it -- s6d_attn.hip, or s6d_attn_f16.hip for 's6d_h::attn_window_kernel<64, 8, false>'.
 """
 import collections
 import os

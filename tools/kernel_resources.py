@@ -1,5 +1,6 @@
 """Static resource usage (VGPR / AGPR / SGPR / scratch / occupancy / static LDS / spills) of every kernel in csrc/*.hip,
 from hipcc's -Rpass-analysis=kernel-resource-usage remarks with the flags the library is built with.  No GPU needed.
+The `file` column is the compiled unit: the attention kernels of csrc/s6d_attn_*.h appear under attn (bf16) and attn_f16 (half).
 
     python tools/kernel_resources.py > profiles/rNN_kernel_resources.txt
 """
