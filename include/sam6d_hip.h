@@ -30,7 +30,7 @@ extern "C" {
 
 /* Bumped whenever a signature in this header changes; the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 125
+#define S6D_ABI_VERSION 126
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -97,9 +97,11 @@ int s6d_segment_seq_sum_f32(const float *x, const int64_t *start, const int64_t 
 /* Point sampler of the PEM pre-processing in its defined form (sam6d_amd/pem/preprocess.py header; reference draws:
  * Pose_Estimation_Model/run_inference_custom.py:224-229, provider/bop_test_dataset.py:140-145).
  * keys (P, key_stride) f32 non-negative uniforms, count (P) i64 candidate points per detection (count <= key_stride),
- * 1 <= n_sample <= 2048 <= key_stride -> idx (P, n_sample) i64: count <= n_sample: floor(key_i * count) (with
+ * 1 <= n_sample <= 6144, n_sample <= key_stride -> idx (P, n_sample) i64: count <= n_sample: floor(key_i * count) (with
  * replacement); else positions of the n_sample smallest (key, position) pairs in ascending order.  overflow (P) i32 is
- * set to 1 for a detection whose keys are too duplicated for the in-LDS selection (its idx row is then not written). */
+ * set to 1 for a detection whose keys are too duplicated for the in-LDS selection (its idx row is then not written).
+ * n_sample <= 2048 (a frame's detections) sorts at most 4096 candidates in LDS, larger ones (the 5000 points of a template
+ * view, run_inference_custom.py:138-141) at most 8192: 64 KiB of composites + the 16 KiB histogram of the CU's 160 KiB. */
 int s6d_pem_sample_indices_f32(const float *keys, long key_stride, const int64_t *count, int P, int n_sample,
                                int64_t *idx, int32_t *overflow, void *stream);
 
@@ -129,6 +131,43 @@ int s6d_pem_radius_filter_f32(const float *center, const double *limit, int P, l
 int s6d_pem_crops_f32(const unsigned char *image, const unsigned char *m, const int64_t *kept, const int64_t *box, int M,
                       int H, int W, int S, int use_mask, const float *mean3_host, const float *std3_host, float *out,
                       void *stream);
+
+/* ---------------------------------------------------------------- Object onboarding from rendered template views
+ * Replace the CPU template loaders of both models (csrc/s6d_onboard.hip; host side: sam6d_amd/onboarding.py). */
+
+/* The two boxes the reference takes from a template mask, in one pass per view.  mask (T,H,W) u8 ->
+ * cnt (T) i64 pixels == 255; box (T,4) i64 [y1,y2,x1,x2]: get_bbox of the pixels == 255 (of the whole view when cnt = 0);
+ * tight (T,4) i64 [x1,y1,x2,y2]: PIL's Image.getbbox of the pixels != 0, upper bounds exclusive (zeros when there is none).
+ * ref: Pose_Estimation_Model/run_inference_custom.py:124-127 + utils/data_utils.py:126-160;
+ * Instance_Segmentation_Model/run_inference_custom.py:131-132. */
+int s6d_template_boxes_u8(const unsigned char *mask, int T, int H, int W, int64_t *cnt, int64_t *box, int64_t *tight,
+                          void *stream);
+
+/* The pixels == 255 of every view's square crop in row-major crop order with their model points.  mask (T,H,W) u8,
+ * xyz_mm (T,H,W,3) f32 millimetres, box (T,4) i64 [y1,y2,x1,x2] inside the view (any other box: n = 0) -> choose (T,cap) i32
+ * crop-flat indices, pts (T,cap,3) f32 = xyz_mm / 1000 (the float32 division of np.float32 / 1000.0), n (T) i64;
+ * cap >= the largest crop area (min(H,W)^2 always suffices).
+ * ref: run_inference_custom.py:123, :128, :137, :143; provider/bop_test_dataset.py:169, :178, :184. */
+int s6d_template_points_f32(const unsigned char *mask, const float *xyz_mm, const int64_t *box, int T, int H, int W, long cap,
+                            int32_t *choose, float *pts, int64_t *n, void *stream);
+
+/* Colour crop of every view: channel-flipped, times (mask == 255) when use_mask, resized to S x S by cv2.resize(INTER_LINEAR)'s
+ * fixed-point arithmetic (copy at 1:1, box average at 2:1), ToTensor + Normalize -- s6d_pem_crops_f32 with one image per crop.
+ * images (T,H,W,3) u8 RGB, mask (T,H,W) u8, box (T,4) i64, mean / std: 3 floats each on the HOST -> out (T,3,S,S) f32 with
+ * channel c = image channel 2 - c.  ref: run_inference_custom.py:130-135; provider/bop_test_dataset.py:171-176. */
+int s6d_template_pem_crops_f32(const unsigned char *images, const unsigned char *mask, const int64_t *box, int T, int H, int W,
+                               int S, int use_mask, const float *mean3_host, const float *std3_host, float *out, void *stream);
+
+/* Template crops for the descriptor model: fl32(u8 / 255) * fl32(mask / 255), then crop . nearest resize . zero pad . nearest
+ * resize; normalize != 0: (v - mean) / std afterwards on every pixel, the padding included (the BOP provider's rgb_transform);
+ * normalize == 0: nothing more (the custom flow).  images (T,H,W,3) u8, mask (T,H,W) u8, params: T records of
+ * s6d_crop_resize_pad_f32 (built on the tight box) -> out_rgb (T,3,S,S) and / or out_mask (T,S,S) f32 = the same crop of
+ * mask / 255; either may be NULL.  mean / std: 3 floats in HOST memory (unused, may be NULL, when normalize == 0).
+ * ref: Instance_Segmentation_Model/run_inference_custom.py:134-151; provider/bop.py:60-83; CropResizePad.__call__,
+ * utils/bbox_utils.py:98-126. */
+int s6d_template_ism_crops_f32(const unsigned char *images, const unsigned char *mask, const void *params, int T, int H, int W,
+                               int S, int normalize, const float *mean3_host, const float *std3_host, float *out_rgb,
+                               float *out_mask, void *stream);
 
 /* ---------------------------------------------------------------- PEM pose solvers
  * Replace the library-op chains of Pose_Estimation_Model/utils/model_utils.py. */

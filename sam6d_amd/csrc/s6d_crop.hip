@@ -10,22 +10,9 @@
 // and the CPU generic kernel use): src = min(floorf(dst * float(1 / scale)), in - 1) with the USER scale_factor, not
 // out / in -- also when out == in (a 17-wide crop "resized" by 1.04 to 17 columns repeats column 0 and drops 16).
 #include "s6d_common.h"
+#include "s6d_crop_params.h"
 
 namespace s6d {
-
-struct CropParams {     // 12 x 4 bytes; all sizes in pixels
-  int x1, y1;           // crop origin in the frame
-  int h, w;             // crop size (box[3]-box[1], box[2]-box[0]: the max corner is EXCLUDED, as in the reference)
-  int h1, w1;           // size after the first resize: floor(h * s1), floor(w * s1)
-  int top, left;        // zero padding in front of the resized crop
-  int S2;               // side of the padded square
-  float inv1, inv2;     // float(1 / s1), float(1 / s2): ATen's compute_scales_value<float>
-  int pad_;
-};
-
-__device__ __forceinline__ int nearest_src(int dst, int in, float inv) {
-  return min((int)floorf((float)dst * inv), in - 1);
-}
 
 __global__ __launch_bounds__(256) void crop_resize_pad_kernel(const unsigned char *__restrict__ image,
                                                               const float *__restrict__ masks,

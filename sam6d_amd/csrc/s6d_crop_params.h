@@ -1,0 +1,25 @@
+// Geometry record of CropResizePad.__call__ (Instance_Segmentation_Model/utils/bbox_utils.py:98-126) and ATen's nearest index rule:
+// shared by the proposal crops (s6d_crop.hip) and the template crops of the onboarding (s6d_onboard.hip).  The host side
+// (sam6d_amd/ism/dinov2.py crop_params) fills one record per crop.
+#pragma once
+#include "s6d_common.h"
+
+namespace s6d {
+
+struct CropParams {     // 12 x 4 bytes; all sizes in pixels
+  int x1, y1;           // crop origin in the frame
+  int h, w;             // crop size (box[3]-box[1], box[2]-box[0]: the max corner is EXCLUDED, as in the reference)
+  int h1, w1;           // size after the first resize: floor(h * s1), floor(w * s1)
+  int top, left;        // zero padding in front of the resized crop
+  int S2;               // side of the padded square
+  float inv1, inv2;     // float(1 / s1), float(1 / s2): ATen's compute_scales_value<float>
+  int pad_;
+};
+
+__device__ __forceinline__ int nearest_src(int dst, int in, float inv) {
+  return min((int)floorf((float)dst * inv), in - 1);
+}
+
+static_assert(sizeof(CropParams) == 48, "CropParams is the 12-int record of include/sam6d_hip.h");
+
+}  // namespace s6d

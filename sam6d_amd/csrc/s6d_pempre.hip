@@ -13,7 +13,8 @@
 //                    Exact, deterministic, independent of the order of the atomics.  Keys must be non-negative floats (their
 //                    bit patterns then order like their values); if more than 4096 keys share the leading bits up to the
 //                    threshold bin (heavily duplicated keys, never uniform ones) the detection is flagged in `overflow` and the
-//                    caller uses the library path for it.
+//                    caller uses the library path for it.  (n_sample > 2048, the 5000 points of a template view: the same kernel
+//                    with 8192 candidates, kSelCapBig below.)
 //   compact_cloud    "mask -> choose -> cloud" of get_test_data (:209-213): the masked pixels of a detection's square crop in
 //                    row-major crop order (``mask[y1:y2, x1:x2].flatten().nonzero()``) with their back-projected points
 //                    (utils/data_utils.py:92-110: x = (u - cx) z / fx, y = (v - cy) z / fy in float32, that operation order).
@@ -22,30 +23,12 @@
 //                    order (wave ballot ranks + a 16-entry wave prefix), writing to the detection's fixed-capacity slot.
 //   radius_filter    ``flag = norm(cloud - center) < radius * 1.2`` (:214-221) and the second in-order compaction, in place.
 #include "s6d_common.h"
+#include "s6d_compact.h"
+#include "s6d_cv_resize.h"
 
 namespace s6d {
 
 #pragma clang fp contract(off)   // the reference's float32 expressions, operation by operation (no fused multiply-adds)
-
-constexpr int kCmpThreads = 1024;
-
-// in-order compaction step of one 1024-element chunk: returns this lane's output position (or -1) and advances *base
-__device__ __forceinline__ long block_rank(bool keep, long *base, unsigned *wave_tot) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long bal = __ballot(keep);
-  const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_tot[wave] = (unsigned)__popcll(bal);
-  __syncthreads();
-  long off = *base;
-  unsigned tot = 0;
-  for (int w = 0; w < kCmpThreads / 64; ++w) {
-    if (w < wave) off += wave_tot[w];
-    tot += wave_tot[w];
-  }
-  __syncthreads();                                      // everyone has read base / wave_tot before they change
-  if (tid == 0) *base += tot;
-  return keep ? off + rank : -1;
-}
 
 // mask (P,H,W) u8 (non-zero = set), depth (H,W) f32 -> m (P,H,W) u8 = mask AND depth > 0, cnt (P) i64, ok (P) u8 = cnt > min_points,
 // box (P,4) i64: get_bbox (utils/data_utils.py:126-160) of m -- of the whole frame for a detection that is not ok, like the
@@ -217,7 +200,12 @@ __global__ __launch_bounds__(kCmpThreads) void radius_filter_kernel(const float 
 
 constexpr int kSelThreads = 1024;
 constexpr int kSelBins = 4096;        // leading 12 bits of the float (sign is 0: 8 exponent + 3 mantissa bits ... see below)
-constexpr int kSelCap = 4096;         // candidates sorted in LDS (32 KB of 64-bit composites)
+constexpr int kSelCap = 4096;         // candidates sorted in LDS (32 KB of 64-bit composites): n_sample <= 2048
+// n_sample up to kSelMaxSample (the 5000 points of a template view, run_inference_custom.py:138-141): the threshold bin is at most
+// 1/16 of the key range below it wide, so uniform keys put about n_sample * 17/16 candidates in front of the sort; 8192 composites
+// are 64 KiB, with the histogram 80 KiB of the CU's 160 KiB LDS -- one workgroup per CU, which 1024 threads allow anyway
+constexpr int kSelCapBig = 8192;
+constexpr int kSelMaxSample = 6144;
 
 // bin of a non-negative float: its 12 leading bits below the sign (exponent + 4 mantissa bits)
 __device__ __forceinline__ unsigned sel_bin(unsigned bits) {
@@ -225,11 +213,12 @@ __device__ __forceinline__ unsigned sel_bin(unsigned bits) {
   return b < (unsigned)kSelBins ? b : (unsigned)kSelBins - 1;    // negative / NaN keys are outside the contract; no wild index
 }
 
+template <int kCap>
 __global__ __launch_bounds__(kSelThreads) void sample_indices_kernel(const float *__restrict__ keys, long key_stride,
                                                                     const long *__restrict__ count, int n_sample,
                                                                     long *__restrict__ idx, int *__restrict__ overflow) {
   __shared__ unsigned hist[kSelBins];
-  __shared__ unsigned long long cand[kSelCap];
+  __shared__ unsigned long long cand[kCap];
   __shared__ unsigned s_thr, s_ncand;
   const int p = blockIdx.x, tid = threadIdx.x;
   const long n = count[p];
@@ -252,7 +241,7 @@ __global__ __launch_bounds__(kSelThreads) void sample_indices_kernel(const float
       if (cum >= (unsigned)n_sample) break;
     }
     s_thr = t;
-    if (cum > (unsigned)kSelCap) s_ncand = 0xffffffffu;  // too many keys up to the threshold bin for the LDS sort
+    if (cum > (unsigned)kCap) s_ncand = 0xffffffffu;  // too many keys up to the threshold bin for the LDS sort
   }
   __syncthreads();
   const unsigned thr = s_thr;
@@ -260,17 +249,17 @@ __global__ __launch_bounds__(kSelThreads) void sample_indices_kernel(const float
     if (tid == 0) overflow[p] = 1;
     return;
   }
-  for (int i = tid; i < kSelCap; i += kSelThreads) cand[i] = ~0ull;
+  for (int i = tid; i < kCap; i += kSelThreads) cand[i] = ~0ull;
   __syncthreads();
   for (long i = tid; i < n; i += kSelThreads) {
     const unsigned b = __float_as_uint(k[i]);
     if (sel_bin(b) <= thr) cand[atomicAdd(&s_ncand, 1u)] = ((unsigned long long)b << 32) | (unsigned long long)i;
   }
   __syncthreads();
-  // bitonic sort of kSelCap 64-bit composites, ascending (the padding ~0 sorts last)
-  for (int size = 2; size <= kSelCap; size <<= 1) {
+  // bitonic sort of kCap 64-bit composites, ascending (the padding ~0 sorts last)
+  for (int size = 2; size <= kCap; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < kSelCap / 2; t += kSelThreads) {
+      for (int t = tid; t < kCap / 2; t += kSelThreads) {
         const int lo = 2 * t - (t & (stride - 1));        // index of the lower element of pair t at this stride
         const int hi = lo + stride;
         const bool up = (lo & size) == 0;
@@ -289,28 +278,8 @@ __global__ __launch_bounds__(kSelThreads) void sample_indices_kernel(const float
 
 // Masked colour crop of every surviving detection, resized to S x S and normalised (run_inference_custom.py:229-236:
 // uint8 crop * uint8 mask, cv2.resize(INTER_LINEAR), ToTensor + Normalize).  The resize is OpenCV's fixed-point algorithm for
-// CV_8U restated exactly (OpenCV 4.x modules/imgproc/src/resize.cpp; oracle/pem_pre.py cv2_resize_linear_u8 is the same
-// statement in numpy): per axis  scale = 1. / (double(S) / n),  f = (float)((o + 0.5) * scale - 0.5),  s = floor(f),  f -= s;
-// x axis: s < 0 -> (0, f = 0), s >= n - 1 -> (n - 1, f = 0); y axis: the two row indices are clipped instead; coefficients
-// saturate_cast<short>((1 - f) * 2048), saturate_cast<short>(f * 2048) (round half to even, each on its own);
-// t = S[sx] a0 + S[sx + 1] a1 per row (int32), dst = (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2.
-// An exact 2:1 ratio on both axes takes OpenCV's area substitute (four-pixel sum + 2) >> 2, a 1:1 ratio is a copy.
+// CV_8U restated exactly (s6d_cv_resize.h, shared with the template crops of s6d_onboard.hip).
 // image (H,W,3) u8 RGB, m (P,H,W) u8, kept (M) i64, box (P,4) i64 -> out (M,3,S,S) f32, channel c = image channel 2 - c.
-__device__ __forceinline__ void cv_linear_tap(int o, int S, long n, bool clamp_index, long &s, int &c0, int &c1) {
-  const double inv = (double)S / (double)n;
-  const double scale = 1.0 / inv;
-  float f = (float)(((double)o + 0.5) * scale - 0.5);
-  const float fl = floorf(f);
-  s = (long)fl;
-  f -= fl;
-  if (clamp_index) {
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= n - 1) { f = 0.f; s = n - 1; }
-  }
-  c0 = (int)fminf(fmaxf(rintf((1.f - f) * 2048.f), -32768.f), 32767.f);
-  c1 = (int)fminf(fmaxf(rintf(f * 2048.f), -32768.f), 32767.f);
-}
-
 __global__ void pem_crops_kernel(const unsigned char *__restrict__ image, const unsigned char *__restrict__ m,
                                  const long *__restrict__ kept, const long *__restrict__ box, int M, int H, int W, int S,
                                  int use_mask, float mean0, float mean1, float mean2, float std0, float std1, float std2,
@@ -328,22 +297,7 @@ __global__ void pem_crops_kernel(const unsigned char *__restrict__ image, const 
       const int v = (int)image[(y * W + x) * 3 + ch];
       return use_mask ? (mp[y * W + x] ? v : 0) : v;
     };
-    int g;
-    if (h == S && w == S) {
-      g = px(oy, ox);
-    } else if (h == 2 * (long)S && w == 2 * (long)S) {
-      g = (px(2 * oy, 2 * ox) + px(2 * oy, 2 * ox + 1) + px(2 * oy + 1, 2 * ox) + px(2 * oy + 1, 2 * ox + 1) + 2) >> 2;
-    } else {
-      long sx, sy;
-      int a0, a1, b0, b1;
-      cv_linear_tap(ox, S, w, true, sx, a0, a1);
-      cv_linear_tap(oy, S, h, false, sy, b0, b1);
-      const long ya = min(max(sy, 0L), h - 1), yb = min(max(sy + 1, 0L), h - 1), xb = min(sx + 1, w - 1);
-      const int t0 = px(ya, sx) * a0 + px(ya, xb) * a1;
-      const int t1 = px(yb, sx) * a0 + px(yb, xb) * a1;
-      g = (((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16) + 2) >> 2;
-      g = min(max(g, 0), 255);
-    }
+    const int g = cv_resize_linear_px(px, oy, ox, h, w, S);
     const float mean = c == 0 ? mean0 : (c == 1 ? mean1 : mean2), sd = c == 0 ? std0 : (c == 1 ? std1 : std2);
     out[i] = ((float)g / 255.f - mean) / sd;
   }
@@ -355,11 +309,15 @@ using namespace s6d;
 
 extern "C" int s6d_pem_sample_indices_f32(const float *keys, long key_stride, const int64_t *count, int P, int n_sample,
                                           int64_t *idx, int32_t *overflow, void *stream) {
-  if (P < 0 || n_sample <= 0 || n_sample > kSelCap / 2 || key_stride < n_sample) return S6D_EINVAL;
+  if (P < 0 || n_sample <= 0 || n_sample > kSelMaxSample || key_stride < n_sample) return S6D_EINVAL;
   if (P == 0) return S6D_OK;
   if (!keys || !count || !idx || !overflow) return S6D_EINVAL;
-  hipLaunchKernelGGL(sample_indices_kernel, dim3((unsigned)P), dim3(kSelThreads), 0, as_stream(stream), keys, key_stride,
-                     (const long *)count, n_sample, (long *)idx, overflow);
+  if (n_sample <= kSelCap / 2)                           // the kernel these sizes have always had: the same bits, the same flag
+    hipLaunchKernelGGL(sample_indices_kernel<kSelCap>, dim3((unsigned)P), dim3(kSelThreads), 0, as_stream(stream), keys, key_stride,
+                       (const long *)count, n_sample, (long *)idx, overflow);
+  else
+    hipLaunchKernelGGL(sample_indices_kernel<kSelCapBig>, dim3((unsigned)P), dim3(kSelThreads), 0, as_stream(stream), keys,
+                       key_stride, (const long *)count, n_sample, (long *)idx, overflow);
   return launch_status();
 }
 

@@ -560,9 +560,12 @@ def segment_seq_sum(x, start, count):
     return out
 
 
+PEM_SAMPLE_MAX = 6144           # n_sample the sampler kernel serves (include/sam6d_hip.h: s6d_pem_sample_indices_f32)
+
+
 def pem_sample_indices(keys, count, n_sample):
     """Sampler of the PEM pre-processing (one workgroup per detection: histogram threshold + in-LDS sort).  keys (P,L) f32
-    uniforms in [0,1), count (P,) int64 (<= L) -> (idx (P,n_sample) int64, overflow (P,) int32)."""
+    uniforms in [0,1), count (P,) int64 (<= L), n_sample <= PEM_SAMPLE_MAX -> (idx (P,n_sample) int64, overflow (P,) int32)."""
     _chk(keys, torch.float32, "keys", 2)
     _chk(count, torch.int64, "count", 1)
     P, L = keys.shape
@@ -637,6 +640,71 @@ def pem_radius_filter(center, limit, choose, cloud, n):
         raise RuntimeError("pem_radius_filter: shape mismatch")
     _call("s6d_pem_radius_filter_f32", _ptr(center), _ptr(limit), P, cap, _ptr(choose), _ptr(cloud), _ptr(n), _stream())
     return n
+
+
+# ------------------------------------------------------------------ object onboarding (csrc/s6d_onboard.hip)
+def _views(mask8, name):
+    _chk(mask8, torch.uint8, "mask", 3)
+    T, H, W = mask8.shape
+    if H * W >= 2 ** 31:
+        raise RuntimeError(f"{name}: a view of {H} x {W} pixels is too large")
+    return T, H, W
+
+
+def template_boxes(mask8):
+    """mask8 (T,H,W) uint8 template masks -> (cnt (T,) int64 pixels == 255, box (T,4) int64 [y1,y2,x1,x2] by the reference's
+    get_bbox over them, tight (T,4) int64 [x1,y1,x2,y2] = PIL getbbox of the pixels != 0)."""
+    T, H, W = _views(mask8, "template_boxes")
+    dev = mask8.device
+    cnt = torch.zeros(T, dtype=torch.int64, device=dev)
+    box = torch.zeros(T, 4, dtype=torch.int64, device=dev)
+    tight = torch.zeros(T, 4, dtype=torch.int64, device=dev)
+    _call("s6d_template_boxes_u8", _ptr(mask8), T, H, W, _ptr(cnt), _ptr(box), _ptr(tight), _stream())
+    return cnt, box, tight
+
+
+def template_points(mask8, xyz_mm, box, cap):
+    """mask8 (T,H,W) uint8, xyz_mm (T,H,W,3) f32, box (T,4) int64 -> (choose (T,cap) int32, pts (T,cap,3) f32 metres, n (T,) int64):
+    the pixels == 255 of every square crop in row-major crop order, one fixed-capacity slot per view."""
+    T, H, W = _views(mask8, "template_points")
+    _chk(xyz_mm, torch.float32, "xyz_mm", 4)
+    _chk(box, torch.int64, "box", 2)
+    if tuple(xyz_mm.shape) != (T, H, W, 3) or tuple(box.shape) != (T, 4):
+        raise RuntimeError("template_points: shape mismatch")
+    choose = torch.empty(T, cap, dtype=torch.int32, device=mask8.device)
+    pts = torch.empty(T, cap, 3, dtype=torch.float32, device=mask8.device)
+    n = torch.zeros(T, dtype=torch.int64, device=mask8.device)
+    _call("s6d_template_points_f32", _ptr(mask8), _ptr(xyz_mm), _ptr(box), T, H, W, cap, _ptr(choose), _ptr(pts), _ptr(n), _stream())
+    return choose, pts, n
+
+
+def template_pem_crops(images_u8, mask8, box, S, use_mask, mean, std):
+    """images (T,H,W,3) uint8, mask8 (T,H,W) uint8, box (T,4) int64 -> (T,3,S,S) f32 normalised, channel-flipped crops."""
+    T, H, W = _views(mask8, "template_pem_crops")
+    _chk(images_u8, torch.uint8, "images", 4)
+    _chk(box, torch.int64, "box", 2)
+    if tuple(images_u8.shape) != (T, H, W, 3) or tuple(box.shape) != (T, 4):
+        raise RuntimeError("template_pem_crops: shape mismatch")
+    out = torch.empty(T, 3, S, S, dtype=torch.float32, device=mask8.device)
+    _call("s6d_template_pem_crops_f32", _ptr(images_u8), _ptr(mask8), _ptr(box), T, H, W, S, bool(use_mask), _float3(mean), _float3(std),
+          _ptr(out), _stream())
+    return out
+
+
+def template_ism_crops(images_u8, mask8, params, S, normalize, mean, std):
+    """images (T,H,W,3) uint8, mask8 (T,H,W) uint8, params (T,12) int32 records (sam6d_amd.ism.dinov2.crop_params on the tight
+    boxes) -> (templates (T,3,S,S) f32, masks (T,S,S) f32)."""
+    T, H, W = _views(mask8, "template_ism_crops")
+    _chk(images_u8, torch.uint8, "images", 4)
+    _chk(params, torch.int32, "params", 2)
+    if tuple(images_u8.shape) != (T, H, W, 3) or tuple(params.shape) != (T, 12):
+        raise RuntimeError("template_ism_crops: shape mismatch")
+    S = int(S)
+    o_rgb = torch.empty(T, 3, S, S, dtype=torch.float32, device=mask8.device)
+    o_mask = torch.empty(T, S, S, dtype=torch.float32, device=mask8.device)
+    _call("s6d_template_ism_crops_f32", _ptr(images_u8), _ptr(mask8), _ptr(params), T, H, W, S, bool(normalize), _float3(mean), _float3(std),
+          _ptr(o_rgb), _ptr(o_mask), _stream())
+    return o_rgb, o_mask
 
 
 def upsample_gather(up, choose, H, W, C):
@@ -1366,7 +1434,9 @@ def have(name):
                "patch_scores": "s6d_patch_scores_sel_f32", "pose_hypotheses": "s6d_pose_hypotheses_f32",
                "pe_group": "s6d_pe_group_mlp_f32", "masked_depth_mean": "s6d_masked_depth_mean_sel_f32",
                "semantic_select": "s6d_semantic_select_f32", "seq_attention": "s6d_seq_attention_bf16", "sam_preprocess": "s6d_sam_preprocess_f32", "im2col3x3": "s6d_im2col3x3_b16", "nonfinite_rows": "s6d_nonfinite_rows_f32", "patchify": "s6d_patchify_b16", "crop_resize_pad": "s6d_crop_resize_pad_f32", "samdec_img2tok": "s6d_samdec_img2tok_bf16", "samdec_img2tok_raw": "s6d_samdec_img2tok_raw_bf16", "samdec_tok2img": "s6d_samdec_tok2img_f32", "samdec_tok2img_raw": "s6d_samdec_tok2img_raw_bf16", "sam_mask_post": "s6d_sam_mask_post_sel_f32", "gemm_fp8_mx": "s6d_gemm_fp8_mxa", "nms": "s6d_nms_f32", "samdec_upscale_heads": "s6d_samdec_upscale_heads_bf16", "samdec_tokens": "s6d_samdec_tokens_post_bf16", "samdec_token_folds": "s6d_samdec_tokens_post_bf16", "mha": "s6d_mha_f32",
-               "linear_attn_focus": "s6d_linear_attn_focus_f32", "linear_attention": "s6d_linear_attention_f32", "project_bbox": "s6d_project_bbox_frames_f32"}.get(name)
+               "linear_attn_focus": "s6d_linear_attn_focus_f32", "linear_attention": "s6d_linear_attention_f32", "project_bbox": "s6d_project_bbox_frames_f32",
+               "template_boxes": "s6d_template_boxes_u8", "template_points": "s6d_template_points_f32", "template_pem_crops": "s6d_template_pem_crops_f32",
+               "template_ism_crops": "s6d_template_ism_crops_f32"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):

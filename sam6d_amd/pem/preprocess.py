@@ -79,7 +79,8 @@ def _cv_taps(lo, hi, S, dev, clamp_index):
 
 def _crops(image_u8, m, box, img_size, rgb_mask_flag):
     """Masked, channel-flipped colour crops resized with cv2.resize(INTER_LINEAR)'s fixed-point arithmetic and normalised:
-    (P,3,S,S) f32 for boxes (P,4).  The library-op statement of pem_crops_kernel (integer for integer the same)."""
+    (P,3,S,S) f32 for boxes (P,4).  The library-op statement of pem_crops_kernel (integer for integer the same).  image_u8
+    (H,W,3): every crop from one frame; (P,H,W,3): one image per crop (the template views of sam6d_amd/onboarding.py)."""
     P = box.shape[0]
     dev = image_u8.device
     S = img_size
@@ -91,7 +92,7 @@ def _crops(image_u8, m, box, img_size, rgb_mask_flag):
 
     def px(yy, xx):                                                                    # (P,S,S,3) crop * mask, crop coordinates
         Y, X = (y1[:, None] + yy)[:, :, None], (x1[:, None] + xx)[:, None, :]
-        v = img[Y, X]
+        v = img[pidx, Y, X] if img.dim() == 4 else img[Y, X]
         return v * mk[pidx, Y, X].unsqueeze(-1) if rgb_mask_flag else v
     sx, a0, a1 = _cv_taps(x1, x2, S, dev, True)
     sy, b0, b1 = _cv_taps(y1, y2, S, dev, False)
@@ -211,28 +212,38 @@ def _finish(image_u8, m, box, kept, pts, ch, img_size, rgb_mask_flag, rgb=None):
     if rgb is None:
         rgb = _crops(image_u8, m[kept].float(), bk, img_size, rgb_mask_flag) if len(kept) else \
             torch.zeros(0, 3, img_size, img_size, device=dev)
+    return dict(pts=pts, rgb=rgb, rgb_choose=resize_rgb_choose(ch, bk, img_size), kept=kept, bbox=bk)
+
+
+def resize_rgb_choose(ch, bk, img_size):
+    """get_resize_rgb_choose for crop-flat indices ch (M,n) i64 of the boxes bk (M,4) [y1,y2,x1,x2] -> (M,n) i64."""
+    dev = ch.device
     ch_h, ch_w = (bk[:, 1] - bk[:, 0]), (bk[:, 3] - bk[:, 2])
     row, col = ch // ch_w[:, None], ch % ch_w[:, None]
     # get_resize_rgb_choose (data_utils.py:113-123) in ITS float64 arithmetic: ratio = fl(img_size / crop) by a true division
     # (`scalar / tensor` is reciprocal() * scalar in torch: one ulp off for crops of 140 or 160 pixels, where row * ratio lands
     # on an integer -- found by the pixels-to-pose golden, round 5), then fl(row * ratio), floor
     size = torch.full((1,), float(img_size), dtype=torch.float64, device=dev)
-    rgb_choose = ((row.double() * torch.div(size, ch_h.double())[:, None]).floor() * img_size +
-                  (col.double() * torch.div(size, ch_w.double())[:, None]).floor()).long()
-    return dict(pts=pts, rgb=rgb, rgb_choose=rgb_choose, kept=kept, bbox=bk)
+    return ((row.double() * torch.div(size, ch_h.double())[:, None]).floor() * img_size +
+            (col.double() * torch.div(size, ch_w.double())[:, None]).floor()).long()
 
 
 def _keyed_indices(n, keys, n_sample):
     """The defined sampler: (P,n_sample) in-list positions from one uniform per crop pixel."""
-    dev = n.device
     use_kernel = _use_kernels(n) and policy.current().pem_sampler != "library"
-    if use_kernel and keys.dtype == torch.float32 and keys.is_contiguous() and n_sample <= 2048:
+    from .. import ops
+    if use_kernel and keys.dtype == torch.float32 and keys.is_contiguous() and n_sample <= ops.PEM_SAMPLE_MAX:
         # one workgroup per detection (s6d_pem_sample_indices_f32) instead of a top-k over a (P, L) table of 64-bit keys; no host
         # round trip for L
-        from .. import ops
         idx, overflow = ops.pem_sample_indices(keys, n.contiguous(), n_sample)
         if not bool(overflow.any()):                                # heavily duplicated keys: the library path below
             return idx
+    return _keyed_indices_library(n, keys, n_sample)
+
+
+def _keyed_indices_library(n, keys, n_sample):
+    """The defined sampler as one top-k over a (P, L) table of 64-bit composite keys."""
+    dev = n.device
     L = int(n.max().item()) if n.numel() else 0                                        # host round trip #2
     L = max(L, n_sample)
     kk = keys[:, :L].float()

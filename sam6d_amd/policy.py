@@ -38,6 +38,7 @@ _ENV = {   # field: (variable, default, type)
     "pem_graph_max": ("S6D_PEM_GRAPH_MAX", 16, int),
     "pem_sampler": ("S6D_PEM_SAMPLER", "", str),                 # "library": torch sampling in the pre-processing
     "pem_pre": ("S6D_PEM_PRE", "", str),                         # "library": torch pre-processing
+    "onboard": ("S6D_ONBOARD", "", str),                         # "library": torch template pre-processing of the onboarding
     "rpe_fold": ("S6D_RPE_FOLD", "1", str),
     "geo_presplit": ("S6D_GEO_PRESPLIT", "1", str),
     "geo_from_points": ("S6D_GEO_FROM_POINTS", "1", str),        # geometric embedding straight from the points; "0": through the idx4 tensor
@@ -70,6 +71,7 @@ class PrecisionPolicy:
     pem_graph_max: int = 16
     pem_sampler: str = ""
     pem_pre: str = ""
+    onboard: str = ""
     rpe_fold: str = "1"
     geo_presplit: str = "1"
     geo_from_points: str = "1"
