@@ -30,7 +30,7 @@ extern "C" {
 
 /* Bumped whenever a signature in this header changes; the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 126
+#define S6D_ABI_VERSION 127
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -189,6 +189,15 @@ int s6d_weighted_procrustes_f32(const float *src, const float *ref, const float 
  * t (B,n_hyp,3), dis (B,n_hyp) = mean_i |(p1_i - t) R - p2_i|. */
 int s6d_pose_hypotheses_f32(const float *pts1, const float *pts2, const int32_t *pair, int B, int N1,
                             int N2, int n_hyp, float *R, float *t, float *dis, void *stream);
+
+/* Feature similarity of the matching heads: atten (B,M1,M2) = normalize(f1) . normalize(f2)^T / temp for f1 (B,M1,C), f2 (B,M2,C)
+ * f32, contiguous and 16-byte aligned.  Per row ss = sum x^2 in an order that depends on C alone, n = max(sqrt(ss), 1e-12f),
+ * x^ = x / n; per element one fma chain over k ascending (the exact-fp32 matrix instruction), then a division by temp
+ * (csrc/s6d_sim.hip states the arithmetic).  An instance has the same bits alone and inside a batch; swapping f1 and f2 gives the
+ * transpose bit for bit; a zero row, and a row whose squares overflow, give exact zeros.  Grid = 32-row panels of f1 x B.
+ * C % 4 == 0 and 4 <= C <= 512, any M1, M2 >= 1: S6D_EUNSUPPORTED otherwise; temp must be finite and > 0.
+ * ref: compute_feature_similarity, utils/model_utils.py:114-136 (cosine, normalize_feat=True). */
+int s6d_cosine_similarity_f32(const float *f1, const float *f2, int B, int M1, int M2, int C, float temp, float *atten, void *stream);
 
 /* Coarse hypothesis sampling: dual softmax of atten (B,M1,M2), background labels, (score[1:,1:])^1.5, float64-accumulated prefix
  * sums normalised by (total + 1e-8), lower-bound search of the caller's uniforms rand_u (B,n_u) -> pair (B,n_u) i32 (flat bin

@@ -150,6 +150,20 @@ def pose_hypotheses(pts1, pts2, pair):
     return R, t, dis
 
 
+def cosine_similarity(f1, f2, temp):
+    """f1 (B,M1,C), f2 (B,M2,C) f32 -> atten (B,M1,M2) f32 = normalize(f1) @ normalize(f2)^T / temp (compute_feature_similarity,
+    cosine) in one launch with a fixed accumulation order per instance: the bits of an instance do not depend on the batch."""
+    _chk(f1, torch.float32, "f1", 3)
+    _chk(f2, torch.float32, "f2", 3)
+    B, M1, C = f1.shape
+    M2 = f2.shape[1]
+    if f2.shape[0] != B or f2.shape[2] != C:
+        raise ValueError(f"cosine_similarity: f1 {tuple(f1.shape)} and f2 {tuple(f2.shape)} must agree in B and C")
+    atten = torch.empty(B, M1, M2, dtype=torch.float32, device=f1.device)
+    _call("s6d_cosine_similarity_f32", _ptr(f1), _ptr(f2), B, M1, M2, C, float(temp), _ptr(atten), _stream())
+    return atten
+
+
 def coarse_sample(atten, rand_u):
     """atten (B,M1,M2) f32, rand_u (B,n_u) f32 -> pair (B,n_u) i32 (flat bin index), w1 (B,M1-1) f32."""
     _chk(atten, torch.float32, "atten", 3)
@@ -1428,7 +1442,7 @@ _FUSED = {}
 def have(name):
     if name not in _FUSED:
         sym = {"rpe_attention": "s6d_rpe_attention_f32", "rpe_attention_packed": "s6d_rpe_attention_packed_f32", "geo_embedding": "s6d_geo_embedding_f32", "geo_embedding_f16": "s6d_geo_embedding_f16", "geo_embedding_split": "s6d_geo_embedding_split", "geo_indices": "s6d_geo_indices_f32", "geo_embedding_points": "s6d_geo_embedding_points_split",
-               "fine_assign": "s6d_fine_assign_f32", "fine_match": "s6d_fine_match_f32", "pem_pre": "s6d_pem_compact_cloud_f32", "coarse_sample": "s6d_coarse_sample_f32", "upsample_gather": "s6d_upsample_gather_f32",
+               "fine_assign": "s6d_fine_assign_f32", "fine_match": "s6d_fine_match_f32", "pem_pre": "s6d_pem_compact_cloud_f32", "coarse_sample": "s6d_coarse_sample_f32", "cosine_similarity": "s6d_cosine_similarity_f32", "upsample_gather": "s6d_upsample_gather_f32",
                "min_dist": "s6d_min_dist_f32", "rot_from_h": "s6d_rot_from_h_f32", "weighted_procrustes": "s6d_weighted_procrustes_f32", "add_layernorm": "s6d_add_layernorm_bf16", "gemm_bf16": "s6d_gemm_bf16", "gemm_bf16_res": "s6d_gemm_bf16_res", "gemm_bf16_lnfold": "s6d_gemm_bf16_lnfold", "gemm_f16": "s6d_gemm_f16", "gemm_fp8": "s6d_gemm_fp8", "layernorm_fp8": "s6d_layernorm_fp8", "layernorm_f32out": "s6d_layernorm_bf16_f32", "linear_f32": "s6d_linear_f32", "attn_output_chain": "s6d_attn_output_chain_f32", "win_attention": "s6d_win_attention_layout_bf16",
                "pairwise_cosine": "s6d_pairwise_cosine_f32",
                "patch_scores": "s6d_patch_scores_sel_f32", "pose_hypotheses": "s6d_pose_hypotheses_f32",

@@ -28,7 +28,16 @@ def _get(cfg, name, default=None):
 
 
 def feature_similarity(f1, f2, temp):
-    """compute_feature_similarity (model_utils.py:114-136), cosine, normalize_feat=True."""
+    """compute_feature_similarity (model_utils.py:114-136), cosine, normalize_feat=True.
+
+    S6D_COARSE_SIM=1: one kernel with a fixed accumulation order per instance (csrc/s6d_sim.hip) -- a batched library GEMM picks its
+    kernel by the batch size, and a last-bit change of `atten` can move a uniform across a bin boundary of the sampling head;
+    "0": the statement below (two normalisations, a transpose, a library bmm and a divide)."""
+    C = f1.shape[-1]
+    if policy.current().coarse_sim == "1" and policy.guard(
+            "pem.feature_similarity", cuda=f1.is_cuda, have=ops.have("cosine_similarity"),
+            f32=f1.dtype == torch.float32 and f2.dtype == torch.float32, C_ok=C % 4 == 0 and 4 <= C <= 512):
+        return ops.cosine_similarity(f1.contiguous(), f2.contiguous(), temp)
     return F.normalize(f1, p=2, dim=2) @ F.normalize(f2, p=2, dim=2).transpose(1, 2) / temp
 
 

@@ -40,12 +40,13 @@ bf16 products = 0.56 of the nominal figure, at ≈ 1.7 – 2.0 GHz under the pow
 | `pchain_kernel<2 / 1>` (s6d_pchain, **round 6**) | a15, a16, a20, a21 | MFMA 3-term bf16 | Linear + residual + LN + FFN 256 → 512 → 256 + residual + LN: attention output and residual read once, y written once (201 MB at M = 65536; h and the 512-wide activations stay on chip); 155 GFLOP executed | {pch['avg_ms']*1e3:.0f} µs at M = 65536 (6 + 24 smaller in 32-row workgroups) | {pch['frac']:.3f} executed ({pch['hbm_gbps']/1e3:.2f} TB/s) |
 | `geo_embed_kernel` (s6d_geo) | a14 | MFMA 3-term bf16 | 650 GFLOP fp32 as written; writes 1.27 GB | {geo['avg_ms']:.2f} ms (2) | {geo['frac']:.3f}; the bare product stream of this kernel: 1.41 of 1.90 ms (`profiles/r06_geo_embed.md`) |
 | `geo_indices_kernel` (s6d_geo) | a14, index stage (`transformer.py:303-332`) | fp32 VALU, cloud in LDS, wave-wide 3-NN selection | points → `knn (B,N,3)` in front of the points-fed `geo_embed_kernel` prologue (or → `idx4` standalone); replaces the library chain matmul / topk / gather / cross / norm / atan2 / cat and its `(B,N,N,3,3)` temporaries | `profiles/geo_from_points.md` | — (O(B·N) output; not a roofline kernel) |
+| `cosine_sim_kernel` (s6d_sim) | a17, similarity (`model_utils.py:114-136`) | exact-fp32 MFMA (`16x16x4_f32`) + fp32 VALU divisions | `normalize(f1) · normalize(f2)ᵀ / temp` in one launch, 32-row panels of `f1` × B workgroups, both operands normalised on the way through LDS; 22 MFLOP per padded 208 × 208 × 256 instance; fixed accumulation order per instance (batch-invariant, transpose-symmetric bit for bit); replaces 8 library launches (2 × norm / clamp / divide, `bmm`, scale) | 38.6 µs per call at 32 instances, 32.6 at 10 against 108.6 / 85.8 for the library statements (`profiles/coarse_similarity.md`) | — (not a roofline kernel) |
 | `rpe_attention_kernel<4,true>` (s6d_rpe) | a15 | HBM | 1.27 GB embedding stream | {rpe['avg_ms']:.3f} ms (12) | {rpe['frac']:.3f} |
 | `pe_group_mlp_kernel` (s6d_pe) | a19 | MFMA 3-term bf16 | 43.7 / 87.3 GFLOP as written (ns = 32 / 64) | 0.24 / 0.36 ms (2 + 2) | 0.22 / 0.30 executed |
 | `fine_split + 3 × fine_sweep_kernel` (s6d_fine) | a22–a23 | MFMA 3-term | 618 GFLOP executed; 4.2 MB / instance | {fine['avg_ms']:.3f} ms (1) | {fine['frac']:.3f} |
 | `samtok_pre / samtok_post_kernel` (s6d_samtok, **round 6**) | f2 | latency / L2 | the sparse-token side of a TwoWayAttentionBlock for 1024 prompts × 7 tokens: 2.9 MB of weights per layer streamed from L2 per 4-prompt workgroup | 25 / 108 µs per launch (2 + 2 per frame), the per-head folds around the attention cores included | replaces ≈ 380 library launches per frame |
 | `img2tok_kernel<RAW>` (s6d_samdec) | f2 | HBM | 2.1 GB read + 2.1 GB written per 1024 prompts | 1.44 – 1.68 ms by box | 0.32 – 0.37 of HBM; LDS conflicts 235 M → 0 this round at unchanged time (`profiles/r06_samdec_ab.md`) |
-| everything else (a1, a6–a13, a17–a19, f-1 … f-4) | | HBM / latency | see `docs/NOTEBOOK_r1_r4.md` §4 | < 1 % of the step each | |
+| everything else (a1, a6–a13, a18–a19, f-1 … f-4; the rest of a17 — the sampling head and the selections — is `s6d_coarse`) | | HBM / latency | see `docs/NOTEBOOK_r1_r4.md` §4 | < 1 % of the step each | |
 
 Stage roofline: SAM ViT-H encoder 5.96 TFLOP × 32 frames in {st['sam_encoder']:.1f} ms = {5.96*32/st['sam_encoder']*1e3:.0f} TFLOP/s = **{5.96*32/st['sam_encoder']/2.5:.3f}** of the nominal peak
 (0.79 of what the chip sustains).  Kernels of this library are 97.4 % of the traced GPU time of the step; library kernels 2.6 %.

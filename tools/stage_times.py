@@ -1,7 +1,10 @@
 """Per-stage wall times of the MI355X PEM path (diagnostic; run on the GPU box):
 python tools/stage_times.py [B]
 python tools/stage_times.py --geo-ab [result.json]   the geo_embedding stage alone, policy field geo_from_points "0" / "1" alternating
-                                                     in this process at 32 and 10 instances (quoted in profiles/geo_from_points.md)"""
+                                                     in this process at 32 and 10 instances (quoted in profiles/geo_from_points.md)
+python tools/stage_times.py --coarse-sim-ab [result.json]   the step from the out_proj outputs to atten alone (pm.feature_similarity), policy
+                                                     field coarse_sim "0" / "1" alternating in this process at 32 and 10 instances (quoted
+                                                     in profiles/coarse_similarity.md)"""
 import json
 import statistics
 import sys
@@ -116,8 +119,49 @@ def geo_ab(path=None, rounds=7, calls=20):
         print(json.dumps(out))
 
 
+def coarse_sim_ab(path=None, rounds=9, calls=50):
+    """pm.feature_similarity on (B,197,256) out_proj-shaped features at temp 0.1: the kernel ("1") against the library statements ("0",
+    two normalisations, a transpose, a bmm and a divide): device-event times of alternating rounds, their medians, the spread of the
+    library rounds (the margin of the comparison), the largest difference of the two results, the device launches of one call."""
+    out = {"rounds": rounds, "calls_per_round": calls, "device": torch.cuda.get_device_name(0)}
+    with torch.no_grad():
+        for B in (32, 10):
+            g = torch.Generator().manual_seed(B)
+            o1 = torch.randn(B, 197, 256, generator=g)
+            o2 = (o1 + 0.2 * torch.randn(B, 197, 256, generator=g)).cuda()
+            o1 = o1.cuda()
+            step = lambda: pm.feature_similarity(o1, o2, 0.1)  # noqa: E731
+            rows = {"0": [], "1": []}
+            for _ in range(rounds):
+                for mode in ("0", "1"):
+                    with policy.use(coarse_sim=mode):
+                        rows[mode].append(round(_event_ms(step, calls) * 1e3, 2))
+            with policy.use(coarse_sim="0"):
+                a = step()
+            with policy.use(coarse_sim="1", strict="1"):
+                b = step()
+            r = {"library_us": rows["0"], "kernel_us": rows["1"], "library_median_us": statistics.median(rows["0"]),
+                 "kernel_median_us": statistics.median(rows["1"]), "library_spread_us": round(max(rows["0"]) - min(rows["0"]), 2),
+                 "max_abs_diff": (a - b).abs().max().item()}
+            r["kernel_no_slower"] = r["kernel_median_us"] <= r["library_median_us"] + r["library_spread_us"]
+            print(B, r, flush=True)
+            for mode, key in (("0", "library_launches"), ("1", "kernel_launches")):
+                with policy.use(coarse_sim=mode):
+                    names = _launches(step)
+                r[key] = {"total": sum(names.values()), "library": sum(v for k, v in names.items() if "s6d" not in k), "by_name": names}
+                print(B, key, r[key]["total"], "library:", r[key]["library"], flush=True)
+            out[f"B{B}"] = r
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+    else:
+        print(json.dumps(out))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--geo-ab":
         geo_ab(sys.argv[2] if len(sys.argv) > 2 else None)
+    elif len(sys.argv) > 1 and sys.argv[1] == "--coarse-sim-ab":
+        coarse_sim_ab(sys.argv[2] if len(sys.argv) > 2 else None)
     else:
         main(int(sys.argv[1]) if len(sys.argv) > 1 else 32)
