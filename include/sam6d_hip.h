@@ -30,7 +30,7 @@ extern "C" {
 
 /* Bumped whenever a signature in this header changes; the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 127
+#define S6D_ABI_VERSION 128
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -168,6 +168,31 @@ int s6d_template_pem_crops_f32(const unsigned char *images, const unsigned char 
 int s6d_template_ism_crops_f32(const unsigned char *images, const unsigned char *mask, const void *params, int T, int H, int W,
                                int S, int normalize, const float *mean3_host, const float *std3_host, float *out_rgb,
                                float *out_mask, void *stream);
+
+/* ---------------------------------------------------------------- Template views rendered from a CAD mesh
+ * Replace the reference's off-device renderers (Render/render_custom_templates.py: BlenderProc;
+ * Instance_Segmentation_Model/utils/poses/pyrender.py: pyrender over EGL) with a compute rasteriser (csrc/s6d_raster.hip, which
+ * states the arithmetic operation by operation). */
+
+/* All T views of one mesh.  vertices (V,3) f32 model units, faces (F,3) i32, colors (V,3) u8, poses (T,4,4) f32 object -> camera
+ * with OpenCV axes (translation in model units); pixel (u, v) is sampled at its integer coordinate.  ->
+ * rgb (T,H,W,3) u8, mask (T,H,W) u8 255 / 0, xyz (T,H,W,3) f32 model coordinates of the visible surface point (perspective-correct
+ * from the model-space vertices; 0 on background), depth (T,H,W) f32 camera Z (0 on background), face (T,H,W) i32 (-1 on
+ * background), skipped (T) i32.
+ * Vertices are projected in float32 and snapped to 1/256 pixel; coverage is decided by int64 edge functions with a top-left fill
+ * rule, winding normalised (no back-face culling), zero-area triangles cover nothing.  Visibility: per pixel the minimum of
+ * (bits(Z) << 32) | face by 64-bit atomicMin: the nearest surface, the lowest face index among equal depths; a view has the same
+ * bits alone and in a batch.  A triangle with a vertex at Z <= znear, a snapped coordinate beyond +-2^23 or a vertex index outside
+ * [0, V) is skipped whole and counted in skipped[view] (no clipping).  Colour = perspective-correct vertex colour x
+ * (ambient + diffuse |n . d|), n the flat face normal, d the direction to the camera, where the light sits; rounded half-to-even.
+ * A triangle whose clamped bounding box holds more than 256 samples is rasterised by a workgroup, smaller ones by one lane.
+ * workspace: s6d_raster_workspace_bytes(T, F, H, W) bytes, 8-byte aligned.  H, W <= 32768 and T * F < 2^31: S6D_EUNSUPPORTED
+ * otherwise; znear >= 0. */
+int s6d_raster_views_f32(const float *vertices, const int32_t *faces, const unsigned char *colors, const float *poses, int V, int F,
+                         int T, int H, int W, float fx, float fy, float cx, float cy, float znear, float ambient, float diffuse,
+                         void *workspace, unsigned char *rgb, unsigned char *mask, float *xyz, float *depth, int32_t *face,
+                         int32_t *skipped, void *stream);
+long s6d_raster_workspace_bytes(int T, int F, int H, int W);   /* -1 for sizes the entry point refuses */
 
 /* ---------------------------------------------------------------- PEM pose solvers
  * Replace the library-op chains of Pose_Estimation_Model/utils/model_utils.py. */

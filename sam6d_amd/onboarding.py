@@ -16,8 +16,9 @@ boxes, in-order compaction, sampling, both kinds of crops; ``onboard`` runs the 
 arguments ``sam6d_amd.pipeline.FramePipeline`` wants.  The same steps are stated with torch ops for host tensors and for
 ``S6D_ONBOARD=library`` runs, behind ``policy.guard``.
 
-Outside this module, as in the reference: rendering, the mesh surface samples (``trimesh.sample``) and the template pose tables --
-the caller passes model points and poses in.
+Rendering the views from a mesh and the mesh surface samples (``trimesh.sample``) are ``sam6d_amd.render`` (``onboard_from_mesh``
+is mesh -> views -> ``onboard``); here the caller passes views, model points and poses in.  Outside the library, as the reference's
+data: the template pose tables.
 
 Defined differently from the reference, on purpose (as for the frame path, sam6d_amd/pem/preprocess.py):
   * sampling uses INJECTED uniforms (``keys``, one per pixel of a view) in the defined form of ``oracle/pem_pre.py``

@@ -721,6 +721,35 @@ def template_ism_crops(images_u8, mask8, params, S, normalize, mean, std):
     return o_rgb, o_mask
 
 
+# ------------------------------------------------------------------ template rendering (csrc/s6d_raster.hip)
+def render_views(vertices, faces, colors, poses, fx, fy, cx, cy, H, W, ambient, diffuse, znear):
+    """vertices (V,3) f32, faces (F,3) int32, colors (V,3) uint8, poses (T,4,4) f32 object -> camera (OpenCV axes) ->
+    dict(rgb (T,H,W,3) uint8, mask (T,H,W) uint8, xyz (T,H,W,3) f32, depth (T,H,W) f32, face (T,H,W) int32, skipped (T,) int32)
+    for all T views (include/sam6d_hip.h: s6d_raster_views_f32).  A face index outside [0, V) is refused here, on the host."""
+    _chk(vertices, torch.float32, "vertices", 2)
+    _chk(faces, torch.int32, "faces", 2)
+    _chk(colors, torch.uint8, "colors", 2)
+    _chk(poses, torch.float32, "poses", 3)
+    V, F, T, H, W = vertices.shape[0], faces.shape[0], poses.shape[0], int(H), int(W)
+    if vertices.shape[1] != 3 or faces.shape[1] != 3 or tuple(colors.shape) != (V, 3) or tuple(poses.shape[1:]) != (4, 4):
+        raise ValueError(f"render_views: vertices (V,3), faces (F,3), colors (V,3), poses (T,4,4) expected, got {tuple(vertices.shape)}, "
+                         f"{tuple(faces.shape)}, {tuple(colors.shape)}, {tuple(poses.shape)}")
+    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise ValueError(f"render_views: face indices must lie in [0, {V}), got [{int(faces.min())}, {int(faces.max())}]")
+    nbytes = _size("s6d_raster_workspace_bytes", T, F, H, W)
+    if nbytes < 0:
+        raise RuntimeError(f"render_views: unsupported sizes (T {T}, F {F}, H {H}, W {W})")
+    dev = vertices.device
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    out = dict(rgb=torch.empty(T, H, W, 3, dtype=torch.uint8, device=dev), mask=torch.empty(T, H, W, dtype=torch.uint8, device=dev),
+               xyz=torch.empty(T, H, W, 3, dtype=torch.float32, device=dev), depth=torch.empty(T, H, W, dtype=torch.float32, device=dev),
+               face=torch.empty(T, H, W, dtype=torch.int32, device=dev), skipped=torch.zeros(T, dtype=torch.int32, device=dev))
+    _call("s6d_raster_views_f32", _ptr(vertices), _ptr(faces), _ptr(colors), _ptr(poses), V, F, T, H, W, float(fx), float(fy), float(cx),
+          float(cy), float(znear), float(ambient), float(diffuse), _ptr(ws), _ptr(out["rgb"]), _ptr(out["mask"]), _ptr(out["xyz"]),
+          _ptr(out["depth"]), _ptr(out["face"]), _ptr(out["skipped"]), _stream())
+    return out
+
+
 def upsample_gather(up, choose, H, W, C):
     """up (B,196,16*C) f32, choose (B,n) int64 -> (B,n,C): bilinear x4 of the pixel-shuffled map at chosen pixels."""
     _chk(up, torch.float32, "up", 3)
@@ -1450,7 +1479,7 @@ def have(name):
                "semantic_select": "s6d_semantic_select_f32", "seq_attention": "s6d_seq_attention_bf16", "sam_preprocess": "s6d_sam_preprocess_f32", "im2col3x3": "s6d_im2col3x3_b16", "nonfinite_rows": "s6d_nonfinite_rows_f32", "patchify": "s6d_patchify_b16", "crop_resize_pad": "s6d_crop_resize_pad_f32", "samdec_img2tok": "s6d_samdec_img2tok_bf16", "samdec_img2tok_raw": "s6d_samdec_img2tok_raw_bf16", "samdec_tok2img": "s6d_samdec_tok2img_f32", "samdec_tok2img_raw": "s6d_samdec_tok2img_raw_bf16", "sam_mask_post": "s6d_sam_mask_post_sel_f32", "gemm_fp8_mx": "s6d_gemm_fp8_mxa", "nms": "s6d_nms_f32", "samdec_upscale_heads": "s6d_samdec_upscale_heads_bf16", "samdec_tokens": "s6d_samdec_tokens_post_bf16", "samdec_token_folds": "s6d_samdec_tokens_post_bf16", "mha": "s6d_mha_f32",
                "linear_attn_focus": "s6d_linear_attn_focus_f32", "linear_attention": "s6d_linear_attention_f32", "project_bbox": "s6d_project_bbox_frames_f32",
                "template_boxes": "s6d_template_boxes_u8", "template_points": "s6d_template_points_f32", "template_pem_crops": "s6d_template_pem_crops_f32",
-               "template_ism_crops": "s6d_template_ism_crops_f32"}.get(name)
+               "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):

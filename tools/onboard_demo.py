@@ -1,8 +1,12 @@
 """Onboard one object from rendered template views and run a frame on it: ``sam6d_amd.onboarding.onboard`` -> ``FramePipeline``.
 
     python tools/onboard_demo.py [TEMPLATE_DIR]          (on the GPU box)
+    python tools/onboard_demo.py --mesh PATH.ply         mesh file -> rendered views -> onboard -> FramePipeline, in this process
 
-With a directory of ``rgb_i.png`` / ``mask_i.png`` / ``xyz_i.npy`` the views are read from it (``load_template_dir``); without one, 42
+With ``--mesh`` the views are rendered on the device (``sam6d_amd.render``: 42 views of 480 x 640 under the LM camera, seeded
+rotations at a distance that lets the object fill about two thirds of the view -- the reference's icosphere pose tables are its
+data and are not shipped), the model / ISM points are ``sample_surface`` draws of the mesh and the whole onboarding is one
+``onboard_from_mesh`` call.  With a directory of ``rgb_i.png`` / ``mask_i.png`` / ``xyz_i.npy`` the views are read from it (``load_template_dir``); without one, 42
 synthetic views of an ellipsoid are made at 512 x 512, the size BlenderProc writes when the render script sets none (the
 reference's Render/ scripts do not).  Seeded weights at the released model sizes; model / ISM points are taken from the views' xyz
 maps and the template poses are identities (the real ones come from the mesh and the icosphere tables, outside this library).
@@ -20,7 +24,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sam6d_amd import onboarding, ops, pipeline  # noqa: E402
+from sam6d_amd import onboarding, ops, pipeline, render  # noqa: E402
 from sam6d_amd.ism import dinov2 as pd  # noqa: E402
 from sam6d_amd.pem import pose_estimation_model as pm  # noqa: E402
 from sam6d_amd.sam.image_encoder import build_vit_h  # noqa: E402
@@ -61,6 +65,36 @@ def object_from_views(rgb, mask, xyz, seed=1):
                 ism_points=surf[r.choice(len(surf), 2048, replace=False)], poses=np.tile(np.eye(4, dtype=np.float32), (len(mask), 1, 1)))
 
 
+MESH_SIZE = (480, 640)
+MESH_K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]])          # the LM camera (pyrender.py:88-91)
+
+
+def mesh_poses(vertices, T=42, seed=0):
+    """T object -> camera poses: seeded rotations about the mesh's centre, which is put on the optical axis at the distance where the
+    bounding sphere spans two thirds of the image height."""
+    g = torch.Generator().manual_seed(seed)
+    R = torch.linalg.qr(torch.randn(T, 3, 3, generator=g, dtype=torch.float64))[0]
+    R = R * torch.linalg.det(R)[:, None, None]                          # proper rotations
+    c = torch.from_numpy((vertices.max(0) + vertices.min(0)) / 2).double()
+    radius = float(np.linalg.norm(vertices - c.numpy(), axis=1).max())
+    P = torch.eye(4, dtype=torch.float64).repeat(T, 1, 1)
+    P[:, :3, :3] = R
+    P[:, :3, 3] = -(R @ c) + torch.tensor([0.0, 0.0, MESH_K[1, 1] * radius / (MESH_SIZE[0] / 3.0)], dtype=torch.float64)
+    return P.float()
+
+
+def object_from_mesh(path, dev):
+    """-> (rgb, mask, xyz numpy views, the object dict of ``onboard``, and the arguments of the equivalent ``onboard_from_mesh`` call)."""
+    vertices, faces, colors = render.load_ply(path)
+    poses = mesh_poses(vertices)
+    views = render.render_templates(vertices, faces, poses.to(dev), MESH_K, MESH_SIZE, colors=colors)
+    su = torch.rand(1, 1024 + 2048, 3, generator=torch.Generator().manual_seed(4))
+    pts = render.sample_surface(torch.from_numpy(vertices), torch.from_numpy(faces), 1024 + 2048, su[0])[0] / torch.full((1,), 1000.0)
+    rgb, mask, xyz = (views[k].cpu().numpy() for k in ("rgb", "mask", "xyz_mm"))
+    obj = dict(rgb=rgb, mask=mask, xyz_mm=xyz, model_points=pts[:1024].numpy(), ism_points=pts[1024:].numpy(), poses=poses.numpy())
+    return rgb, mask, xyz, obj, dict(meshes=[(vertices, faces, colors)], poses=poses.to(dev), surface_uniforms=su)
+
+
 def models(dev):
     dino = pd.CustomDINOv2.__new__(pd.CustomDINOv2)
     torch.nn.Module.__init__(dino)
@@ -83,14 +117,28 @@ def timed(fn):
 
 def main():
     dev = torch.device("cuda", 0)
-    rgb, mask, xyz = onboarding.load_template_dir(sys.argv[1]) if len(sys.argv) > 1 else synthetic_views()
+    mesh = sys.argv[2] if len(sys.argv) > 2 and sys.argv[1] == "--mesh" else None
+    if mesh:
+        rgb, mask, xyz, obj, mesh_args = object_from_mesh(mesh, dev)
+    else:
+        rgb, mask, xyz = onboarding.load_template_dir(sys.argv[1]) if len(sys.argv) > 1 else synthetic_views()
+        obj = object_from_views(rgb, mask, xyz)
     T, H, W = mask.shape
-    obj = object_from_views(rgb, mask, xyz)
     dino, net = models(dev)
     keys = torch.rand(1, T, H * W, generator=torch.Generator().manual_seed(2)).to(dev)
     d_rgb, d_mask, d_xyz = (torch.from_numpy(a).to(dev) for a in (rgb, mask, xyz))
     res = dict(views=T, height=H, width=W, n_sample=5000, img_size=224)
-    res["onboard_ms"], onb = timed(lambda: onboarding.onboard(dino, net, [obj], keys=keys, n_view=T))
+    if mesh:
+        v, f, c = mesh_args["meshes"][0]
+        res.update(mesh=os.path.basename(mesh), vertices=len(v), faces=len(f), covered_pixels_per_view=int((mask == 255).sum()) // T)
+        res["render_ms"], _ = timed(lambda: render.render_templates(v, f, mesh_args["poses"], MESH_K, MESH_SIZE, colors=c))
+        res["onboard_ms"], onb = timed(lambda: render.onboard_from_mesh(dino, net, mesh_args["meshes"], mesh_args["poses"], MESH_K, MESH_SIZE,
+                                                                        surface_uniforms=mesh_args["surface_uniforms"], keys=keys, n_view=T))
+        ref = onboarding.onboard(dino, net, [obj], keys=keys, n_view=T)
+        res["equals_onboard_on_the_views"] = bool(torch.equal(onb.pem_templates["dense_fo"], ref.pem_templates["dense_fo"]) and
+                                                  torch.equal(onb.scorer.ref_data["descriptors"], ref.scorer.ref_data["descriptors"]))
+    else:
+        res["onboard_ms"], onb = timed(lambda: onboarding.onboard(dino, net, [obj], keys=keys, n_view=T))
     res["pem_pre_ms"], (tem_rgb, tem_pts, tem_choose) = timed(lambda: onboarding.pem_template_inputs(d_rgb, d_mask, d_xyz, keys=keys[0]))
     res["ism_pre_ms"], (tem, msk) = timed(lambda: onboarding.ism_template_inputs(d_rgb, d_mask, 224))
     cnt, box, _ = ops.template_boxes(d_mask)

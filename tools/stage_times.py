@@ -4,7 +4,11 @@ python tools/stage_times.py --geo-ab [result.json]   the geo_embedding stage alo
                                                      in this process at 32 and 10 instances (quoted in profiles/geo_from_points.md)
 python tools/stage_times.py --coarse-sim-ab [result.json]   the step from the out_proj outputs to atten alone (pm.feature_similarity), policy
                                                      field coarse_sim "0" / "1" alternating in this process at 32 and 10 instances (quoted
-                                                     in profiles/coarse_similarity.md)"""
+                                                     in profiles/coarse_similarity.md)
+python tools/stage_times.py --render [result.json]   ops.render_views alone: 42 views of 480 x 640 of a 45,600-face torus (one lane per
+                                                     triangle) and of a 12-face cube (a workgroup per triangle), beside the time of
+                                                     one device copy of the key buffer -- its bytes read once and written once at the
+                                                     copy rate, the floor of the visibility pass (quoted in profiles/render.md)"""
 import json
 import statistics
 import sys
@@ -158,8 +162,55 @@ def coarse_sim_ab(path=None, rounds=9, calls=50):
         print(json.dumps(out))
 
 
+def render_times(path=None, rounds=5, calls=200):
+    """ops.render_views on the two work shapes at the reference's template size (42 views, 480 x 640, the LM camera of
+    Instance_Segmentation_Model/utils/poses/pyrender.py:88-91): device-event times per call (workspace allocation and the face-index
+    check of the wrapper included), the covered pixels, the triangles the workgroup kernel took, and the copy of the key buffer."""
+    import numpy as np
+
+    from sam6d_amd import ops
+    from tests import render_ref as R
+    T, H, W = 42, 480, 640
+    K = (572.4114, 573.57043, 325.2611, 242.04899)
+    out = {"views": T, "height": H, "width": W, "rounds": rounds, "calls_per_round": calls, "device": torch.cuda.get_device_name(0)}
+    # the floor of the visibility pass: the key buffer written once and read once = one copy of it.  Copied back to back, source and
+    # destination (2 x 103 MB) stay in the 256 MiB last-level cache, which is also how the three render launches meet the buffer;
+    # rotating over eight pairs (1.65 GB) makes every copy come from and go to HBM.
+    pairs = [(torch.zeros(T, H, W, dtype=torch.int64, device="cuda"), torch.empty(T, H, W, dtype=torch.int64, device="cuda")) for _ in range(8)]
+    out["key_buffer_bytes"] = pairs[0][0].numel() * 8
+    state = {"i": 0}
+
+    def rotate():
+        src, dst = pairs[state["i"] % 8]
+        state["i"] += 1
+        dst.copy_(src)
+    for key, fn in (("cached", lambda: pairs[0][1].copy_(pairs[0][0])), ("hbm", rotate)):
+        rows = [round(_event_ms(fn, 400), 4) for _ in range(rounds)]
+        out[f"key_buffer_copy_{key}_ms"] = rows
+        out[f"key_buffer_copy_{key}_median_ms"] = statistics.median(rows)
+        out[f"copy_rate_{key}_GBps"] = round(2 * out["key_buffer_bytes"] / statistics.median(rows) / 1e6, 1)
+    del pairs[1:]
+    for name, (v, f, c), z in (("torus_45600_faces", R.torus(152, 150), 300.0), ("cube_12_faces", R.cube(), 300.0)):
+        P = R.poses(T, seed=1, t=(0.0, 0.0, z))
+        tv, tf, tc, tp = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (v, f, c, P))
+        step = lambda: ops.render_views(tv, tf, tc, tp, *K, H, W, 0.3, 0.7, 1.0)  # noqa: E731
+        rows = [round(_event_ms(step, calls), 4) for _ in range(rounds)]
+        res = step()
+        r = {"faces": int(tf.shape[0]), "ms": rows, "median_ms": statistics.median(rows), "covered_pixels_per_view": int((res["mask"] == 255).sum()) // T,
+             "skipped": int(res["skipped"].sum()), "launches": _launches(step)}
+        print(name, r, flush=True)
+        out[name] = r
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+    else:
+        print(json.dumps(out))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--geo-ab":
+    if len(sys.argv) > 1 and sys.argv[1] == "--render":
+        render_times(sys.argv[2] if len(sys.argv) > 2 else None)
+    elif len(sys.argv) > 1 and sys.argv[1] == "--geo-ab":
         geo_ab(sys.argv[2] if len(sys.argv) > 2 else None)
     elif len(sys.argv) > 1 and sys.argv[1] == "--coarse-sim-ab":
         coarse_sim_ab(sys.argv[2] if len(sys.argv) > 2 else None)
