@@ -30,7 +30,7 @@ extern "C" {
 
 /* Bumped whenever a signature in this header changes; the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 128
+#define S6D_ABI_VERSION 129
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -193,6 +193,47 @@ int s6d_raster_views_f32(const float *vertices, const int32_t *faces, const unsi
                          void *workspace, unsigned char *rgb, unsigned char *mask, float *xyz, float *depth, int32_t *face,
                          int32_t *skipped, void *stream);
 long s6d_raster_workspace_bytes(int T, int F, int H, int W);   /* -1 for sizes the entry point refuses */
+
+/* The depth of T views of one mesh alone, a camera per view: poses (T,4,4) f32, cams (T,4) f32 = fx fy cx cy of the view ->
+ * depth (T,H,W) f32 camera Z (0 on background), skipped (T) i32.  The vertex stage, the set-up, the coverage rule and the depth
+ * statement are those of s6d_raster_views_f32, so a pixel holds the bits that entry point writes to `depth` for the same view and
+ * camera, and skipped is the same count; both work shapes are kept (a lane per triangle, a workgroup per triangle whose clamped
+ * box holds more than 256 samples).  The visibility key is bits(Z) alone, reduced with a 32-bit atomicMin in the depth output
+ * itself; a camera that is not finite makes every triangle of its view skipped.
+ * workspace: s6d_raster_depth_workspace_bytes(T, F, H, W) bytes, 8-byte aligned (the list of large triangles: no key buffer).
+ * Sizes as s6d_raster_views_f32; znear >= 0. */
+int s6d_raster_depth_f32(const float *vertices, const int32_t *faces, const float *poses, const float *cams, int V, int F, int T,
+                         int H, int W, float znear, void *workspace, float *depth, int32_t *skipped, void *stream);
+long s6d_raster_depth_workspace_bytes(int T, int F, int H, int W);   /* -1 for sizes the entry point refuses */
+
+/* ---------------------------------------------------------------- BOP pose errors (csrc/s6d_boperr.hip)
+ * The errors behind the BOP average recall -- MSSD, MSPD and the per-pixel stage of VSD -- as DEFINED in csrc/s6d_boperr.hip,
+ * operation by operation in float32 with one rounding each.  bop_toolkit is not part of this project; nothing here claims
+ * equality with its output. */
+
+/* N estimates of ONE object against their ground truths under S symmetries.  vertices (V,3) f32 model units, est (N,4,4) f32
+ * object -> camera, gts (N,S,4,4) f32 = the ground-truth pose composed with every symmetry (on the host, in float64, rounded
+ * once), cams (N,4) f32 = fx fy cx cy ->
+ *   mssd[n] = min_s max_v |E_n v - G_ns v|                 (model units)
+ *   mspd[n] = min_s max_v |proj(E_n v) - proj(G_ns v)|     (pixels), proj(P) = ((fx X) / Z + cx, (fy Y) / Z + cy)
+ * with X = ((r00 vx + r01 vy) + r02 vz) + tx, squared distances (dx dx + dy dy) + dz dz and du du + dv dv, one sqrtf of the
+ * maximum.  A vertex with Z <= 0 in either pose makes that symmetry's MSPD +inf; a distance that is not finite (a NaN pose)
+ * makes the symmetry's value +inf.  One workgroup per (n, s), one atomicMin per output on the float's bits: an instance has the
+ * same bits alone and in a batch.  V >= 1, S >= 1, N >= 0; N * S < 2^31, S6D_EUNSUPPORTED otherwise. */
+int s6d_pose_err_mssd_mspd_f32(const float *vertices, const float *est, const float *gts, const float *cams, int V, int N, int S,
+                               float *mssd, float *mspd, void *stream);
+
+/* Pixel counts of VSD for N (estimate, ground truth) pairs.  depth_est, depth_gt (N,H,W) f32 rendered camera Z (0 = background),
+ * depth_test (M,H,W) f32 measured camera Z in the same unit (0 = missing), test_index (N) i32 into M, cams (N,4) f32,
+ * scale (N) f32, taus: NT <= 16 floats in HOST memory ->  union (N) i32, inter (N) i32, ge (N,NT) i32.
+ * At pixel (u, v):  a = ((float)u - cx) / fx, b = ((float)v - cy) / fy, r = sqrtf((a a + b b) + 1), D = Z r (distance from the
+ * camera centre);  vis_gt = Zg > 0 && ((Dg - Dt) <= delta || Zt == 0);  vis_est = Ze > 0 && (((De - Dt) <= delta || Zt == 0) ||
+ * vis_gt);  union counts vis_gt || vis_est, inter counts both, and on inter ge[k] counts fabsf(Dg - De) / scale[n] >= taus[k].
+ * The VSD error at taus[k] is (ge[k] + union - inter) / union, 1 for an empty union: formed by the caller.  Integer atomics:
+ * exact and reproducible.  A test_index outside [0, M) leaves the pair's counts 0.  H * W < 2^31. */
+int s6d_vsd_counts_f32(const float *depth_est, const float *depth_gt, const float *depth_test, const int32_t *test_index,
+                       const float *cams, const float *scale, int N, int M, int H, int W, float delta, const float *taus_host,
+                       int NT, int32_t *uni, int32_t *inter, int32_t *ge, void *stream);
 
 /* ---------------------------------------------------------------- PEM pose solvers
  * Replace the library-op chains of Pose_Estimation_Model/utils/model_utils.py. */

@@ -7,6 +7,7 @@ Package layout (only what the hot path needs):
   pem/         drop-in Pose_Estimation_Model modules (Net, ViTEncoder, matching heads)
   sam/         drop-in SAM ImageEncoderViT
   ism/         drop-in ISM scoring classes
+  evaluation.py  BOP pose errors (MSSD, MSPD, VSD) and their average recall, on the device
   utils/       seeded weights / synthetic frames, ADD(-S) metrics, frame sharding
 """
 __version__ = "0.1.0"

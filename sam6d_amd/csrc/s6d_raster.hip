@@ -242,6 +242,77 @@ __global__ __launch_bounds__(RASTER_THREADS) void raster_resolve_kernel(const fl
   }
 }
 
+// ---- depth alone, a camera per view (s6d_raster_depth_f32: the two renders of a VSD evaluation, csrc/s6d_boperr.hip) ----------------
+// The same vertex stage, set-up, coverage rule and depth statement as above, so a pixel holds the depth bits the full render gives
+// it.  The visibility key is bits(Z) alone (Z > 0: the bits order like the value), reduced with atomicMin on unsigned IN the depth
+// output, preset to all ones; a last pass turns what is still all ones into 0.  The workspace is the list of large triangles only.
+constexpr unsigned RASTER_EMPTY32 = ~0u;
+
+__device__ __forceinline__ RasterCam raster_view_cam(const float *__restrict__ cams, int t, float znear) {
+  const float *k = cams + (size_t)t * 4;
+  return RasterCam{k[0], k[1], k[2], k[3], znear};
+}
+
+__device__ __forceinline__ void raster_sample_depth(const RasterTri &tr, int u, int v, unsigned *__restrict__ key) {
+  long w[3];
+  if (!raster_covers(tr, u, v, w)) return;
+  float q[3];
+  const float z = 1.0f / raster_weights(tr, w, q);
+  atomicMin(key, __float_as_uint(z));
+}
+
+__global__ __launch_bounds__(RASTER_THREADS) void raster_depth_small_kernel(const float *__restrict__ vertices, const int *__restrict__ faces,
+                                                                            const float *__restrict__ poses, const float *__restrict__ cams,
+                                                                            int V, int F, int T, int H, int W, float znear,
+                                                                            unsigned *__restrict__ keys, int *__restrict__ large_list,
+                                                                            int *__restrict__ large_count, int *__restrict__ skipped) {
+  const long i = (long)blockIdx.x * RASTER_THREADS + threadIdx.x;
+  if (i >= (long)T * F) return;
+  const int t = (int)(i / F), f = (int)(i - (long)t * F);
+  const RasterCam c = raster_view_cam(cams, t, znear);
+  RasterTri tr;
+  const int st = raster_setup(vertices, faces, poses, V, t, f, c, H, W, tr);
+  if (st < 0) atomicAdd(&skipped[t], 1);
+  if (st <= 0) return;
+  if ((long)(tr.u1 - tr.u0 + 1) * (tr.v1 - tr.v0 + 1) > RASTER_LARGE_BOX) {
+    large_list[atomicAdd(large_count, 1)] = (int)i;                      // at most T * F appends: the list's size
+    return;
+  }
+  unsigned *kp = keys + (size_t)t * H * W;
+  for (int v = tr.v0; v <= tr.v1; ++v)
+    for (int u = tr.u0; u <= tr.u1; ++u) raster_sample_depth(tr, u, v, kp + (size_t)v * W + u);
+}
+
+__global__ __launch_bounds__(RASTER_THREADS) void raster_depth_large_kernel(const float *__restrict__ vertices, const int *__restrict__ faces,
+                                                                            const float *__restrict__ poses, const float *__restrict__ cams,
+                                                                            int V, int F, int H, int W, float znear,
+                                                                            unsigned *__restrict__ keys, const int *__restrict__ large_list,
+                                                                            const int *__restrict__ large_count) {
+  const int count = *large_count;
+  for (int e = blockIdx.x; e < count; e += gridDim.x) {
+    const int i = large_list[e];
+    const int t = i / F, f = i - t * F;
+    const RasterCam c = raster_view_cam(cams, t, znear);
+    RasterTri tr;
+    if (raster_setup(vertices, faces, poses, V, t, f, c, H, W, tr) <= 0) continue;
+    const int bw = tr.u1 - tr.u0 + 1;
+    const long n = (long)bw * (tr.v1 - tr.v0 + 1);
+    unsigned *kp = keys + (size_t)t * H * W;
+    for (long j = threadIdx.x; j < n; j += RASTER_THREADS) {
+      const int r = (int)(j / bw), v = tr.v0 + r, u = tr.u0 + (int)(j - (long)r * bw);
+      raster_sample_depth(tr, u, v, kp + (size_t)v * W + u);
+    }
+  }
+}
+
+__global__ __launch_bounds__(RASTER_THREADS) void raster_depth_resolve_kernel(unsigned *__restrict__ keys, size_t total) {
+  for (size_t p = (size_t)blockIdx.x * RASTER_THREADS + threadIdx.x; p < total; p += (size_t)gridDim.x * RASTER_THREADS)
+    if (keys[p] == RASTER_EMPTY32) keys[p] = 0u;                         // the bits of 0.f: background
+}
+
+// workspace of the depth render: list (T F) i32 | the list's length (one i32, padded to 8 bytes)
+__host__ inline long raster_depth_count_offset(int T, int F) { return ((long)T * F * 4 + 7) & ~7L; }
+
 // workspace: keys (T,H,W) u64 | list (T F) i32 | the list's length (one i32, padded to 8 bytes)
 __host__ inline long raster_list_offset(int T, int H, int W) { return (long)T * H * W * 8; }
 __host__ inline long raster_count_offset(int T, int F, int H, int W) { return raster_list_offset(T, H, W) + (((long)T * F * 4 + 7) & ~7L); }
@@ -302,5 +373,48 @@ extern "C" int s6d_raster_views_f32(const float *vertices, const int32_t *faces,
   if (g > 65536) g = 65536;
   hipLaunchKernelGGL(raster_resolve_kernel, dim3((unsigned)g), dim3(RASTER_THREADS), 0, s, vertices, faces, colors, poses, V, T, H, W, c,
                      ambient, diffuse, keys, rgb, mask, xyz, depth, face);
+  return launch_status();
+}
+
+extern "C" long s6d_raster_depth_workspace_bytes(int T, int F, int H, int W) {
+  if (!raster_sizes_ok(0, F, T, H, W) || !raster_sizes_supported(F, T, H, W)) return -1;
+  return raster_depth_count_offset(T, F) + 8;
+}
+
+extern "C" int s6d_raster_depth_f32(const float *vertices, const int32_t *faces, const float *poses, const float *cams, int V, int F,
+                                    int T, int H, int W, float znear, void *workspace, float *depth, int32_t *skipped, void *stream) {
+  if (!raster_sizes_ok(V, F, T, H, W)) return S6D_EINVAL;
+  if (!(znear >= 0.f && znear <= 3.402823466e+38f)) return S6D_EINVAL;
+  if (!raster_sizes_supported(F, T, H, W)) return S6D_EUNSUPPORTED;
+  if (T == 0) return S6D_OK;
+  if (!poses || !cams || !workspace || !depth || !skipped || (F > 0 && (!vertices || !faces))) return S6D_EINVAL;
+  if ((uintptr_t)workspace & 7) return S6D_EINVAL;
+  hipStream_t s = as_stream(stream);
+  char *ws = reinterpret_cast<char *>(workspace);
+  unsigned *keys = reinterpret_cast<unsigned *>(depth);
+  int *list = reinterpret_cast<int *>(ws);
+  int *count = reinterpret_cast<int *>(ws + raster_depth_count_offset(T, F));
+  const size_t total = (size_t)T * H * W;
+  hipError_t e = hipMemsetAsync(keys, 0xff, total * 4, s);
+  if (e == hipSuccess) e = hipMemsetAsync(count, 0, 8, s);
+  if (e == hipSuccess) e = hipMemsetAsync(skipped, 0, (size_t)T * 4, s);
+  if (e != hipSuccess) {
+    set_hip_error(e);
+    return S6D_ELAUNCH;
+  }
+  const long pairs = (long)T * F;
+  if (pairs > 0) {
+    hipLaunchKernelGGL(raster_depth_small_kernel, dim3((unsigned)((pairs + RASTER_THREADS - 1) / RASTER_THREADS)), dim3(RASTER_THREADS), 0,
+                       s, vertices, faces, poses, cams, V, F, T, H, W, znear, keys, list, count, skipped);
+    const int rc = launch_status();
+    if (rc != S6D_OK) return rc;
+    hipLaunchKernelGGL(raster_depth_large_kernel, dim3((unsigned)(pairs < RASTER_LARGE_GRID ? pairs : RASTER_LARGE_GRID)),
+                       dim3(RASTER_THREADS), 0, s, vertices, faces, poses, cams, V, F, H, W, znear, keys, list, count);
+    const int rc2 = launch_status();
+    if (rc2 != S6D_OK) return rc2;
+  }
+  size_t g = (total + RASTER_THREADS - 1) / RASTER_THREADS;
+  if (g > 65536) g = 65536;
+  hipLaunchKernelGGL(raster_depth_resolve_kernel, dim3((unsigned)g), dim3(RASTER_THREADS), 0, s, keys, total);
   return launch_status();
 }

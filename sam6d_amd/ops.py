@@ -750,6 +750,81 @@ def render_views(vertices, faces, colors, poses, fx, fy, cx, cy, H, W, ambient, 
     return out
 
 
+def render_depth(vertices, faces, poses, cams, H, W, znear):
+    """vertices (V,3) f32, faces (F,3) int32, poses (T,4,4) f32 object -> camera, cams (T,4) f32 = fx fy cx cy per view ->
+    dict(depth (T,H,W) f32 camera Z, 0 on background; skipped (T,) int32): the depth bits of ``render_views`` for the same view and
+    camera (include/sam6d_hip.h: s6d_raster_depth_f32).  A face index outside [0, V) is refused here, on the host."""
+    _chk(vertices, torch.float32, "vertices", 2)
+    _chk(faces, torch.int32, "faces", 2)
+    _chk(poses, torch.float32, "poses", 3)
+    _chk(cams, torch.float32, "cams", 2)
+    V, F, T, H, W = vertices.shape[0], faces.shape[0], poses.shape[0], int(H), int(W)
+    if vertices.shape[1] != 3 or faces.shape[1] != 3 or tuple(poses.shape[1:]) != (4, 4) or tuple(cams.shape) != (T, 4):
+        raise ValueError(f"render_depth: vertices (V,3), faces (F,3), poses (T,4,4), cams (T,4) expected, got {tuple(vertices.shape)}, "
+                         f"{tuple(faces.shape)}, {tuple(poses.shape)}, {tuple(cams.shape)}")
+    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise ValueError(f"render_depth: face indices must lie in [0, {V}), got [{int(faces.min())}, {int(faces.max())}]")
+    nbytes = _size("s6d_raster_depth_workspace_bytes", T, F, H, W)
+    if nbytes < 0:
+        raise RuntimeError(f"render_depth: unsupported sizes (T {T}, F {F}, H {H}, W {W})")
+    dev = vertices.device
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    out = dict(depth=torch.empty(T, H, W, dtype=torch.float32, device=dev), skipped=torch.zeros(T, dtype=torch.int32, device=dev))
+    _call("s6d_raster_depth_f32", _ptr(vertices), _ptr(faces), _ptr(poses), _ptr(cams), V, F, T, H, W, float(znear), _ptr(ws),
+          _ptr(out["depth"]), _ptr(out["skipped"]), _stream())
+    return out
+
+
+# ------------------------------------------------------------------ BOP pose errors (csrc/s6d_boperr.hip)
+def pose_errors(vertices, est, gts, cams):
+    """vertices (V,3) f32, est (N,4,4) f32 object -> camera, gts (N,S,4,4) f32 ground truths composed with the S symmetries,
+    cams (N,4) f32 = fx fy cx cy -> (mssd (N,) f32 model units, mspd (N,) f32 pixels): the minimum over the symmetries of the
+    maximum over the vertices (include/sam6d_hip.h: s6d_pose_err_mssd_mspd_f32)."""
+    _chk(vertices, torch.float32, "vertices", 2)
+    _chk(est, torch.float32, "est", 3)
+    _chk(gts, torch.float32, "gts", 4)
+    _chk(cams, torch.float32, "cams", 2)
+    V, N, S = vertices.shape[0], est.shape[0], gts.shape[1]
+    if vertices.shape[1] != 3 or tuple(est.shape[1:]) != (4, 4) or tuple(gts.shape) != (N, S, 4, 4) or tuple(cams.shape) != (N, 4):
+        raise ValueError(f"pose_errors: vertices (V,3), est (N,4,4), gts (N,S,4,4), cams (N,4) expected, got {tuple(vertices.shape)}, "
+                         f"{tuple(est.shape)}, {tuple(gts.shape)}, {tuple(cams.shape)}")
+    mssd = torch.empty(N, dtype=torch.float32, device=vertices.device)
+    mspd = torch.empty(N, dtype=torch.float32, device=vertices.device)
+    _call("s6d_pose_err_mssd_mspd_f32", _ptr(vertices), _ptr(est), _ptr(gts), _ptr(cams), V, N, S, _ptr(mssd), _ptr(mspd), _stream())
+    return mssd, mspd
+
+
+def vsd_counts(depth_est, depth_gt, depth_test, test_index, cams, delta, taus, scale):
+    """depth_est, depth_gt (N,H,W) f32 rendered depths, depth_test (M,H,W) f32 measured depth in the same unit (0 = missing),
+    test_index (N,) int32 into M, cams (N,4) f32, delta, taus (a sequence of at most 16 floats), scale (N,) f32 ->
+    (union (N,) int32, inter (N,) int32, ge (N,NT) int32): the pixel counts of VSD (include/sam6d_hip.h: s6d_vsd_counts_f32).
+    A test_index outside [0, M) is refused here, on the host."""
+    _chk(depth_est, torch.float32, "depth_est", 3)
+    _chk(depth_gt, torch.float32, "depth_gt", 3)
+    _chk(depth_test, torch.float32, "depth_test", 3)
+    _chk(test_index, torch.int32, "test_index", 1)
+    _chk(cams, torch.float32, "cams", 2)
+    _chk(scale, torch.float32, "scale", 1)
+    N, H, W = depth_est.shape
+    M = depth_test.shape[0]
+    tau = [float(x) for x in (taus.tolist() if hasattr(taus, "tolist") else taus)]
+    NT = len(tau)
+    if tuple(depth_gt.shape) != (N, H, W) or tuple(depth_test.shape[1:]) != (H, W) or tuple(test_index.shape) != (N,) or \
+            tuple(cams.shape) != (N, 4) or tuple(scale.shape) != (N,):
+        raise ValueError(f"vsd_counts: depth_est, depth_gt (N,H,W), depth_test (M,H,W), test_index (N,), cams (N,4), scale (N,) expected, got "
+                         f"{tuple(depth_est.shape)}, {tuple(depth_gt.shape)}, {tuple(depth_test.shape)}, {tuple(test_index.shape)}, "
+                         f"{tuple(cams.shape)}, {tuple(scale.shape)}")
+    if N and (int(test_index.min()) < 0 or int(test_index.max()) >= M):
+        raise ValueError(f"vsd_counts: test_index must lie in [0, {M}), got [{int(test_index.min())}, {int(test_index.max())}]")
+    dev = depth_est.device
+    union = torch.empty(N, dtype=torch.int32, device=dev)
+    inter = torch.empty(N, dtype=torch.int32, device=dev)
+    ge = torch.empty(N, NT, dtype=torch.int32, device=dev)
+    _call("s6d_vsd_counts_f32", _ptr(depth_est), _ptr(depth_gt), _ptr(depth_test), _ptr(test_index), _ptr(cams), _ptr(scale), N, M, H, W,
+          float(delta), (ctypes.c_float * max(NT, 1))(*tau), NT, _ptr(union), _ptr(inter), _ptr(ge), _stream())
+    return union, inter, ge
+
+
 def upsample_gather(up, choose, H, W, C):
     """up (B,196,16*C) f32, choose (B,n) int64 -> (B,n,C): bilinear x4 of the pixel-shuffled map at chosen pixels."""
     _chk(up, torch.float32, "up", 3)
@@ -1479,7 +1554,8 @@ def have(name):
                "semantic_select": "s6d_semantic_select_f32", "seq_attention": "s6d_seq_attention_bf16", "sam_preprocess": "s6d_sam_preprocess_f32", "im2col3x3": "s6d_im2col3x3_b16", "nonfinite_rows": "s6d_nonfinite_rows_f32", "patchify": "s6d_patchify_b16", "crop_resize_pad": "s6d_crop_resize_pad_f32", "samdec_img2tok": "s6d_samdec_img2tok_bf16", "samdec_img2tok_raw": "s6d_samdec_img2tok_raw_bf16", "samdec_tok2img": "s6d_samdec_tok2img_f32", "samdec_tok2img_raw": "s6d_samdec_tok2img_raw_bf16", "sam_mask_post": "s6d_sam_mask_post_sel_f32", "gemm_fp8_mx": "s6d_gemm_fp8_mxa", "nms": "s6d_nms_f32", "samdec_upscale_heads": "s6d_samdec_upscale_heads_bf16", "samdec_tokens": "s6d_samdec_tokens_post_bf16", "samdec_token_folds": "s6d_samdec_tokens_post_bf16", "mha": "s6d_mha_f32",
                "linear_attn_focus": "s6d_linear_attn_focus_f32", "linear_attention": "s6d_linear_attention_f32", "project_bbox": "s6d_project_bbox_frames_f32",
                "template_boxes": "s6d_template_boxes_u8", "template_points": "s6d_template_points_f32", "template_pem_crops": "s6d_template_pem_crops_f32",
-               "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32"}.get(name)
+               "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32",
+               "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):

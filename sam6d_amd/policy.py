@@ -43,6 +43,7 @@ _ENV = {   # field: (variable, default, type)
     "geo_presplit": ("S6D_GEO_PRESPLIT", "1", str),
     "geo_from_points": ("S6D_GEO_FROM_POINTS", "1", str),        # geometric embedding straight from the points; "0": through the idx4 tensor
     "coarse_sim": ("S6D_COARSE_SIM", "1", str),                  # feature similarity of the matching heads as one kernel; "0": the library statements
+    "bop_eval": ("S6D_BOP_EVAL", "1", str),                      # BOP pose errors (sam6d_amd.evaluation) as kernels; "0": the library statements
     "desc_group": ("S6D_DESC_GROUP", "1", str),                  # descriptors of a frame group in one DINOv2 pass
     "gemm_res": ("S6D_GEMM_RES", "0", str),
     "lnfold": ("S6D_LNFOLD", "1", str),
@@ -77,6 +78,7 @@ class PrecisionPolicy:
     geo_presplit: str = "1"
     geo_from_points: str = "1"
     coarse_sim: str = "1"
+    bop_eval: str = "1"
     desc_group: str = "1"
     gemm_res: str = "0"
     lnfold: str = "1"

@@ -1,0 +1,97 @@
+"""Score a BOP result file with sam6d_amd.evaluation (MSSD, MSPD, VSD and their average recall, BOP19 parameters):
+
+python tools/bop_eval.py --results X.csv --dataset DIR [--split test] [--device cuda|cpu]
+
+X.csv: the lines ``pem.results.write_bop_csv`` writes (``scene,im,obj,score,R,t,time``; what FramePipeline and tools/run_sharded.py
+produce).  DIR: a dataset in the BOP layout --
+  DIR/models_eval/models_info.json, DIR/models_eval/obj_000001.ply ...      the evaluation models (``render.load_ply`` reads them)
+  DIR/<split>/<scene:06d>/scene_gt.json, scene_camera.json, depth/<im:06d>.png      (the scenes directly under DIR when there is no
+                                                                                    DIR/<split>)
+  DIR/<split>/<scene:06d>/scene_gt_info.json   optional: the targets are the ground truths with visib_fract >= 0.1; all of them when
+                                               the file is absent
+Every image named in the scenes' ground truth that the result file's scenes cover is scored; depth PNGs are 16 bit, times
+``depth_scale`` = millimetres.  Prints one JSON line.
+
+bop_toolkit is not part of this project: the errors follow the definitions restated in sam6d_amd/evaluation.py and
+csrc/s6d_boperr.hip, and no equality with the toolkit's numbers is claimed."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def load_dataset(root, split, scenes, min_visib=0.1):
+    """-> (models {obj: dict}, ground_truths dict, images dict, index {(scene, im): image number})."""
+    from PIL import Image
+
+    from sam6d_amd import render
+    base = os.path.join(root, split) if os.path.isdir(os.path.join(root, split)) else root
+    with open(os.path.join(root, "models_eval", "models_info.json")) as f:
+        info = {int(k): v for k, v in json.load(f).items()}
+    index, cams, depths = {}, [], []
+    gt = dict(im=[], obj=[], pose=[])
+    for scene in sorted(scenes):
+        d = os.path.join(base, f"{scene:06d}")
+        with open(os.path.join(d, "scene_gt.json")) as f:
+            scene_gt = {int(k): v for k, v in json.load(f).items()}
+        with open(os.path.join(d, "scene_camera.json")) as f:
+            scene_cam = {int(k): v for k, v in json.load(f).items()}
+        gt_info = None
+        if os.path.exists(os.path.join(d, "scene_gt_info.json")):
+            with open(os.path.join(d, "scene_gt_info.json")) as f:
+                gt_info = {int(k): v for k, v in json.load(f).items()}
+        for im in sorted(scene_gt):
+            K = np.asarray(scene_cam[im]["cam_K"], np.float64).reshape(3, 3)
+            depth = np.asarray(Image.open(os.path.join(d, "depth", f"{im:06d}.png")), np.float32) * np.float32(scene_cam[im].get("depth_scale", 1.0))
+            index[(scene, im)] = len(cams)
+            cams.append([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+            depths.append(depth)
+            for j, g in enumerate(scene_gt[im]):
+                if gt_info is not None and float(gt_info[im][j].get("visib_fract", 1.0)) < min_visib:
+                    continue
+                P = np.eye(4)
+                P[:3, :3] = np.asarray(g["cam_R_m2c"], np.float64).reshape(3, 3)
+                P[:3, 3] = np.asarray(g["cam_t_m2c"], np.float64).reshape(3)
+                gt["im"].append(index[(scene, im)])
+                gt["obj"].append(int(g["obj_id"]))
+                gt["pose"].append(P)
+    if len({d.shape for d in depths}) > 1:
+        raise ValueError(f"depth images of different sizes: {sorted({d.shape for d in depths})}")
+    models = {}
+    for obj in sorted(set(gt["obj"])):
+        v, f, _ = render.load_ply(os.path.join(root, "models_eval", f"obj_{obj:06d}.ply"))
+        models[obj] = dict(vertices=v, faces=f, info=info[obj], diameter=float(info[obj]["diameter"]))
+    images = dict(cams=np.asarray(cams, np.float32).reshape(-1, 4), depth=np.stack(depths) if depths else np.zeros((0, 1, 1), np.float32))
+    gt = dict(im=np.asarray(gt["im"], np.int64), obj=np.asarray(gt["obj"], np.int64), pose=np.asarray(gt["pose"], np.float64).reshape(-1, 4, 4))
+    return models, gt, images, index
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--results", required=True)
+    ap.add_argument("--dataset", required=True)
+    ap.add_argument("--split", default="test")
+    ap.add_argument("--device", default=None, help="cuda (kernels) or cpu (the torch statements); default: cuda when there is one")
+    a = ap.parse_args(argv)
+    from sam6d_amd import evaluation
+    t0 = time.time()
+    res = evaluation.read_bop_csv(a.results)
+    models, gt, images, index = load_dataset(a.dataset, a.split, set(res["scene"].tolist()))
+    keep = np.array([(int(s), int(i)) in index for s, i in zip(res["scene"], res["im"])], bool)
+    pose = np.tile(np.eye(4), (int(keep.sum()), 1, 1))
+    pose[:, :3, :3], pose[:, :3, 3] = res["R"][keep], res["t"][keep]
+    est = dict(im=np.array([index[(int(s), int(i))] for s, i in zip(res["scene"][keep], res["im"][keep])], np.int64), obj=res["obj"][keep],
+               score=res["score"][keep], pose=pose)
+    out = evaluation.bop19_scores(models, est, gt, images, device=a.device)
+    out.update(results=os.path.basename(a.results), images=len(index), dropped_estimates=int((~keep).sum()), seconds=round(time.time() - t0, 3))
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

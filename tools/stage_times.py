@@ -8,7 +8,12 @@ python tools/stage_times.py --coarse-sim-ab [result.json]   the step from the ou
 python tools/stage_times.py --render [result.json]   ops.render_views alone: 42 views of 480 x 640 of a 45,600-face torus (one lane per
                                                      triangle) and of a 12-face cube (a workgroup per triangle), beside the time of
                                                      one device copy of the key buffer -- its bytes read once and written once at the
-                                                     copy rate, the floor of the visibility pass (quoted in profiles/render.md)"""
+                                                     copy rate, the floor of the visibility pass (quoted in profiles/render.md)
+python tools/stage_times.py --bop-eval [result.json]   the BOP pose errors (sam6d_amd.evaluation): kernels beside the library statements in
+                                                     this process -- MSSD / MSPD of 256 estimates, 20,000 vertices, 1 and 315 symmetries;
+                                                     the two depth renders and the pixel stage of VSD at 480 x 640 with 10 taus --
+                                                     with the launches and the peak requested bytes of either branch and the floor of
+                                                     the pixel stage (quoted in profiles/bop_eval.md)"""
 import json
 import statistics
 import sys
@@ -207,8 +212,90 @@ def render_times(path=None, rounds=5, calls=200):
         print(json.dumps(out))
 
 
+def _peak_bytes(fn):
+    """requested_bytes.all.peak of one call above what was held before it."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_stats()["requested_bytes.all.current"]
+    fn()
+    torch.cuda.synchronize()
+    return int(torch.cuda.memory_stats()["requested_bytes.all.peak"] - before)
+
+
+def bop_eval_times(path=None, rounds=5):
+    """ops.pose_errors / ops.render_depth / ops.vsd_counts beside the torch statements of sam6d_amd.evaluation: device-event times
+    (median of `rounds` rounds), device launches of one call, peak requested bytes of one call, and for the pixel stage of VSD the
+    time of reading its three depth images once at the measured HBM copy rate."""
+    import numpy as np
+
+    from sam6d_amd import evaluation as ev
+    from sam6d_amd import ops
+    from tests import bop_ref as B
+    from tests import render_ref as R
+    N, V, H, W = 256, 20000, 480, 640
+    out = {"estimates": N, "vertices": V, "height": H, "width": W, "rounds": rounds, "device": torch.cuda.get_device_name(0)}
+    rs = np.random.RandomState(0)
+    v = torch.from_numpy(rs.uniform(-60, 60, (V, 3)).astype(np.float32)).cuda()
+    gt = B.seeded_poses(N, seed=1)
+    est = gt.copy()
+    est[:, :3, 3] += rs.uniform(-6, 6, (N, 3))
+    e = torch.from_numpy(est.astype(np.float32)).cuda()
+    cams = torch.tensor([[572.4114, 573.57043, 325.2611, 242.04899]]).repeat(N, 1).cuda()
+
+    def measure(fn, calls):
+        rows = [round(_event_ms(fn, calls), 4) for _ in range(rounds)]
+        return {"ms": rows, "median_ms": statistics.median(rows), "launches": _launches(fn), "peak_requested_bytes": _peak_bytes(fn)}
+    for S in (1, 315):
+        g = torch.from_numpy((gt[:, None] @ B.axis_symmetries(S)[None]).astype(np.float32)).cuda()
+        r = {"kernel": measure(lambda: ops.pose_errors(v, e, g, cams), 20), "library": measure(lambda: ev._pose_errors_library(v, e, g, cams), 1 if S > 1 else 5)}
+        k, lib = ops.pose_errors(v, e, g, cams), ev._pose_errors_library(v, e, g, cams)
+        r["max_abs_difference"] = [float((k[0] - lib[0]).abs().max()), float((k[1] - lib[1]).abs().max())]
+        print(f"mssd_mspd_S{S}", r, flush=True)
+        out[f"mssd_mspd_S{S}"] = r
+    # VSD: a 45,600-face torus at 256 perturbed poses, the measured depth = the ground-truth render with noise and holes
+    tv, tf, _ = R.torus(152, 150)
+    tv, tf = torch.from_numpy(tv).cuda(), torch.from_numpy(tf).cuda()
+    pg = R.poses(N, seed=1, t=(0.0, 0.0, 400.0)).astype(np.float64)
+    pe = pg.copy()
+    pe[:, :3, 3] += rs.uniform(-8, 8, (N, 3))
+    pg, pe = torch.from_numpy(pg.astype(np.float32)).cuda(), torch.from_numpy(pe.astype(np.float32)).cuda()
+    out["render_depth"] = measure(lambda: ops.render_depth(tv, tf, pe, cams, H, W, 1.0), 10)
+    de, dg = ops.render_depth(tv, tf, pe, cams, H, W, 1.0)["depth"], ops.render_depth(tv, tf, pg, cams, H, W, 1.0)["depth"]
+    test = torch.where(dg > 0, dg + 3 * torch.randn_like(dg), torch.full_like(dg, 900.0))
+    test[torch.rand_like(test) < 0.1] = 0
+    ti = torch.arange(N, dtype=torch.int32).cuda()
+    scale = torch.full((N,), 170.0).cuda()
+    taus = list(ev.BOP19["vsd_taus"])
+    out["vsd_counts"] = {"kernel": measure(lambda: ops.vsd_counts(de, dg, test, ti, cams, 15.0, taus, scale), 20),
+                         "library": measure(lambda: ev._vsd_counts_library(de, dg, test, ti, cams, 15.0, taus, scale), 2)}
+    a, b = ops.vsd_counts(de, dg, test, ti, cams, 15.0, taus, scale), ev._vsd_counts_library(de, dg, test, ti, cams, 15.0, taus, scale)
+    out["vsd_counts"]["counts_differ_at_most"] = max(int((x - y).abs().max()) for x, y in zip(a, b))
+    out["vsd_counts"]["mean_union"] = float(a[0].float().mean())
+    # the floor of the pixel stage: its three inputs read once.  The copy rate comes from copies that rotate over buffers larger than
+    # the last-level cache together (4 x 2 x 315 MB)
+    nbytes = 3 * de.numel() * 4
+    pairs = [(torch.zeros_like(de), torch.empty_like(de)) for _ in range(4)]
+    state = {"i": 0}
+
+    def rotate():
+        src, dst = pairs[state["i"] % 4]
+        state["i"] += 1
+        dst.copy_(src)
+    rows = [round(_event_ms(rotate, 40), 4) for _ in range(rounds)]
+    rate = 2 * de.numel() * 4 / statistics.median(rows) / 1e6
+    out["vsd_counts"].update(input_bytes=nbytes, copy_rate_hbm_GBps=round(rate, 1), floor_ms=round(nbytes / rate / 1e6, 4))
+    print("vsd", out["render_depth"], out["vsd_counts"], flush=True)
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+    else:
+        print(json.dumps(out))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--render":
+    if len(sys.argv) > 1 and sys.argv[1] == "--bop-eval":
+        bop_eval_times(sys.argv[2] if len(sys.argv) > 2 else None)
+    elif len(sys.argv) > 1 and sys.argv[1] == "--render":
         render_times(sys.argv[2] if len(sys.argv) > 2 else None)
     elif len(sys.argv) > 1 and sys.argv[1] == "--geo-ab":
         geo_ab(sys.argv[2] if len(sys.argv) > 2 else None)
