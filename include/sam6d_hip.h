@@ -30,7 +30,7 @@ extern "C" {
 
 /* Bumped whenever a signature in this header changes; the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 129
+#define S6D_ABI_VERSION 130
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -39,9 +39,16 @@ int s6d_set_persistent_grid_limit(int max_workgroups);
 /* Which form of the bf16 / f16 GEMM kernel serves the shapes both forms cover (csrc/s6d_gemm.hip: eight waves, 128 x 64 wave tiles;
  * csrc/s6d_gemm4.hip: four waves, 128 x 128 wave tiles, accumulators in the accumulator register file): 0 = the library's choice per
  * shape (the default: the eight-wave form, measured 0.3 % ahead inside the benched step), 64 = always the eight-wave form, 128 = the
- * four-wave form wherever it applies (bf16 / f16, N % 256 == 0, M % 256 == 0, K >= 128).  Both forms give the same bits (the same products in the same order per
- * accumulator); the switch exists for A/B measurements and the parity tests.  Process-wide; returns S6D_EINVAL for other values. */
+ * four-wave form wherever it applies (bf16 / f16, N % 256 == 0, M % 256 == 0, K >= 128).  The two PINNED forms (64 against 128) give the same bits (the same products
+ * in the same order per accumulator: a pinned wave tile also pins the 32x32x16 matrix instruction, see s6d_set_gemm_mfma_shape); the switch exists for A/B measurements and the parity tests.  Process-wide; returns S6D_EINVAL for other values. */
 int s6d_set_gemm_wave_tile(int columns);
+/* Which bf16 matrix instruction the eight-wave form and the 256 x 128 tile form of the GEMM use: 32 = v_mfma_f32_32x32x16_bf16,
+ * 16 = v_mfma_f32_16x16x32_bf16 (same tiles, schedule and LDS traffic; the hardware's summation order inside the two instructions
+ * differs, so their results may differ in the last bit of an output), 0 = the library's choice (the default): 16 while the wave tile
+ * is not pinned, 32 under s6d_set_gemm_wave_tile(64 | 128).  An explicit 16 keeps the four-wave form (32x32x16 only) out.  The two
+ * tile forms give each other's bits under either shape.  fp8 and IEEE-half products are not affected.  Process-wide; returns
+ * S6D_EINVAL for other values. */
+int s6d_set_gemm_mfma_shape(int rows);
 /* 1 (default): a plain or GELU bf16 / f16 GEMM launch that would put fewer than 160 tiles of 256 x 256 on the chip takes the 256 x 128
  * tile kernel (two independent workgroups per CU) -- the PEM ViT-B's 6304 x 768 products are 75 tiles otherwise.  0: always the
  * 256 x 256 kernel.  2: as 1, and the residual + row-statistics epilogue (the ViT-H's proj / lin2 at one frame) as well -- built and

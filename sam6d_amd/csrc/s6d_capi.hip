@@ -33,6 +33,16 @@ extern "C" int s6d_set_gemm_wave_tile(int columns) {
   return S6D_OK;
 }
 
+// Shape of the bf16 matrix instruction in the eight-wave and the 256 x 128 GEMM form (include/sam6d_hip.h: s6d_set_gemm_mfma_shape).
+namespace s6d {
+int g_s6d_gemm_mfma_shape = 0;
+}
+extern "C" int s6d_set_gemm_mfma_shape(int rows) {
+  if (rows != 0 && rows != 16 && rows != 32) return S6D_EINVAL;
+  s6d::g_s6d_gemm_mfma_shape = rows;
+  return S6D_OK;
+}
+
 // 256 x 128 tiles for the plain / GELU GEMM launches that would leave most CUs idle (include/sam6d_hip.h: s6d_set_gemm_small_tile).
 namespace s6d {
 int g_s6d_gemm_small_tile = 1;

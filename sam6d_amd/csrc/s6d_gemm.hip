@@ -28,6 +28,8 @@
 //   * epilogue in registers: bias is the accumulator's initial value, erf-form GELU as relu(x) - |x| 2^P(|x|) (gelu_erf below:
 //     relative error 6e-6), round to bf16,
 //     v_permlane32_swap pairs the two lane halves into 16-byte row segments.
+//   * MI (template parameter of gemm_body / gemm2_bf16_kernel): the bf16 matrix instruction, 32 = 32x32x16 as described here, 16 =
+//     16x16x32 on the same schedule (see gemm_body); selected per launch (s6d_set_gemm_mfma_shape, gemm_launch).
 #include "s6d_common.h"
 #include "s6d_gemm_params.h"
 #include <stdlib.h>
@@ -183,8 +185,28 @@ __device__ __forceinline__ unsigned pack_out(float lo, float hi) {
 // EPI 5 (DT = 1): C = e4m3(GELU(A W^T + bias)) with MX scales -- in the quad-transposed accumulator layout ONE lane holds a whole
 // 32-column block of its row (columns 32 h + {0..31} of the wave's 64), so the block maximum, the scale and the 32 bytes are
 // lane-local: no exchange, two 16-byte stores and one scale byte per lane and m tile.
-template <int EPI, bool HAS_BIAS, int DT, bool AMX = false>
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+// MI (the M = N of the bf16 matrix instruction): 32 = v_mfma_f32_32x32x16_bf16 as described above; 16 = v_mfma_f32_16x16x32_bf16 on
+// the SAME tile schedule, ring, LDS image, waits and barriers (bf16 operands, two-phase loop, EPI 0 - 4 only).  What changes:
+//   * a wave's 128 x 64 share is 8 (m) x 4 (n) tiles of 16 x 16 (32 accumulator quads = the same 128 registers); a K tile is two
+//     k steps of 32; a phase is 4 m tiles x 4 n tiles x 2 k steps = 32 MFMAs of half the cycles, k step outer, tile inner;
+//   * fragment read: lane -> row lane & 15, chunk 4 ks + (lane >> 4): one ds_read_b128 per 16-row fragment and k step, 16 fragments
+//     per phase as before.  Activation rows are read in order (conflict-free under the swizzle: the two chunks a ds_read_b128 lane
+//     group mixes differ in bit 0, the rows' keys cover 0..7 once per row parity);
+//   * W rows are fed PERMUTED: matrix row a = 4 g + r of n tile nt is W row 32 (g & 1) + 16 (g >> 1) + 4 r + (nt ^ (g >> 1)) of the
+//     wave's 64.  (i) The 16 rows of a fragment are distinct mod 16, with the parity bit of lane groups 2, 3 flipped against 0, 1 --
+//     that is what keeps the read conflict-free where two lane groups share a ds_read_b128 group.  (ii) In the accumulators lane
+//     group g = lane >> 4 then owns the 16 columns 32 (g & 1) + 16 (g >> 1) + {0..15} of output row lane & 15 (+ 16 per m tile),
+//     register r of tile nt = column 4 r + (nt ^ (g >> 1)) of them;
+//   * epilogue: one v_permlane32_swap per accumulator pair of m tiles 2 s, 2 s + 1 gives the lower lane half row 32 s + (lane & 15)
+//     and the upper half row 32 s + 16 + (lane & 15), each with the 32 CONSECUTIVE columns 32 h + {0..31}, h = (lane >> 4) & 1,
+//     in a fixed register order -- the lane layout of the 32x32x16 epilogue, whose arithmetic (statistics summed in ascending column
+//     order, rstd, GELU, rounding), quad transpose and 64-bytes-per-quad stores then run unchanged.
+template <int EPI, bool HAS_BIAS, int DT, bool AMX = false, int MI = 32>
 __device__ __forceinline__ void gemm_body(const GemmParams &p) {
+  static_assert(MI == 32 || (MI == 16 && DT == 0 && EPI <= 4 && S6D_GEMM_QT && S6D_GEMM_PH2),
+                "the 16x16x32 shape is wired for bf16 operands, the two-phase loop and the quad-transposed epilogue");
   static_assert(!AMX || DT == 1, "MX block scales belong to the fp8 operands");
   static_assert(EPI != 5 || (DT == 1 && S6D_GEMM_QT), "the MX output is the fp8 kernel's, on the quad-transposed layout");
   const int tid = threadIdx.x, lane = tid & 63;
@@ -306,6 +328,27 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
 
   f32x16 acc[4][2];                                                      // [m tile][n tile], transposed: lane -> m, regs -> n
   bf16x8 xf[2][4], wf[2][4];                                             // activation rows (2 m tiles), W rows (2 n tiles) x 4 k steps
+  // MI = 16: lane group lg owns 16 columns from c16 of the wave's 64; the upper lane half (up) holds them with column pairs swapped
+  const int lg = lane >> 4, up = lane >> 5, c16 = 32 * (lg & 1) + 16 * up;
+  unsigned foff6[2], wfo6[4][2];
+  if constexpr (MI == 16) {
+    const int a = lane & 15;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) foff6[ks] = (unsigned)(a * 128 + (((4 * ks + lg) ^ ((a >> 1) & 7)) << 4));
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int gp = a >> 2, row = 32 * (gp & 1) + 16 * (gp >> 1) + 4 * (a & 3) + (nt ^ (gp >> 1));
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) wfo6[nt][ks] = brow + (unsigned)(row * 128 + (((4 * ks + lg) ^ ((row >> 1) & 7)) << 4));
+    }
+  }
+  f32x4 acc6[8][4];                                                      // MI = 16: [m tile of 16 rows][n tile]
+  bf16x8 xf6[4][2], wf6[4][2];                                           // 4 m tiles / 4 n tiles x 2 k steps
+  // row of a 32-row strip, column half and first row of the lane quad in the EPILOGUE layout (MI = 16: after the lane-half swap).
+  // (macros, not variables: the 32x32x16 instantiations keep the expressions where they were, hence their code)
+#define S6D_LROW (MI == 16 ? 16 * (lane >> 5) + (lane & 15) : (lane & 31))
+#define S6D_LH (MI == 16 ? ((lane >> 4) & 1) : (lane >> 5))
+#define S6D_LQ (MI == 16 ? 16 * (lane >> 5) + (lane & 12) : (lane & 28))
   int ct = 0, ck = 0;                                                    // compute cursor
   int cm0, cn0;
   tile_mn(0, cm0, cn0);
@@ -355,7 +398,18 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   // spends there anyway: the HBM latency of a tile that no other workgroup shares hides behind a whole epilogue.
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   u32x4 rn[4][4];
+  u32x4 rn6[8][2];                                                       // MI = 16: [m tile][8-column piece] of this lane group's 16 columns
   auto load_resid = [&](int mt, int m0, int n0) __attribute__((always_inline)) {
+    if constexpr (MI == 16) {                                            // strip mt = m tiles 2 mt, 2 mt + 1, in the accumulator layout
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int m = min(m0 + wr * 128 + (2 * mt + i) * 16 + (lane & 15), p.M - 1);
+        const char *src = (const char *)p.R + (size_t)m * p.ldr2 + (size_t)(n0 + wc * 64 + c16) * 2;
+        rn6[2 * mt + i][0] = *reinterpret_cast<const u32x4 *>(src);
+        rn6[2 * mt + i][1] = *reinterpret_cast<const u32x4 *>(src + 16);
+      }
+      return;
+    }
     const int m = min(m0 + wr * 128 + mt * 32 + (lane & 31), p.M - 1);     // rows past M: a valid address, never stored
     const char *src = (const char *)p.R + (size_t)m * p.ldr2 + (size_t)(n0 + wc * 64 + 32 * (lane >> 5)) * 2;
 #pragma unroll
@@ -370,6 +424,51 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     // rstd_m (x W'^T - mean_m s) + b'.  Everything the fold needs is fetched HERE, next to the bias loads' drain: a load in the
     // epilogue would have to wait (in-order counter) for the next tile's LDS-DMA prefetch, still on its way from HBM -- measured
     // 2 us per tile, + 6 % on qkv and lin1.
+    if constexpr (MI == 16) {
+      // register r of n tile nt: column c16 + 4 r + (nt ^ up) of the wave's 64, read per lane; the pair swap of the upper lane half
+      // sits in the address: even nt reads at + up, odd nt at - up
+      // (pinned: per-lane offsets hoisted out of the tile loop would live through the K loop)
+      int be = n0 + wc * 64 + c16 + up, bo = n0 + wc * 64 + c16 - up;
+      S6D_PIN(be);
+      S6D_PIN(bo);
+      const float *bse = p.bias + be, *bso = p.bias + bo, *cse = p.CS + be, *cso = p.CS + bo;
+      float sig6[8], nmu6[8];
+      if (EPI == 3 || EPI == 4) {
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt) {
+          const int m = min(m0 + wr * 128 + mt * 16 + (lane & 15), p.M - 1);   // rows past M: a valid address, never stored
+          const float2 st = *reinterpret_cast<const float2 *>(p.RS + (size_t)m * 2);
+          nmu6[mt] = -st.x;
+          sig6[mt] = st.y;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) ln_rs[s] = __builtin_amdgcn_rcpf(up ? sig6[2 * s + 1] : sig6[2 * s]);   // the row the swap leaves here
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          const float b = HAS_BIAS ? ((nt & 1) ? bso[4 * r + nt] : bse[4 * r + nt]) : 0.f;
+          if (EPI == 3 || EPI == 4) {
+            const float sn = (nt & 1) ? cso[4 * r + nt] : cse[4 * r + nt];
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) acc6[mt][nt][r] = fmaf(sig6[mt], b, nmu6[mt] * sn);
+          } else if (EPI == 2) {
+            // columns 4 r + {2 j, 2 j + 1} (j = nt >> 1) are one dword of the residual row; the upper lane half takes them swapped
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) {
+              const unsigned w0 = rn6[mt][r >> 1][2 * (r & 1) + (nt >> 1)];
+              const unsigned w = up ? ((w0 >> 16) | (w0 << 16)) : w0;
+              acc6[mt][nt][r] = b + __uint_as_float((nt & 1) ? (w & 0xffff0000u) : (w << 16));
+            }
+          } else {
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) acc6[mt][nt][r] = b;
+          }
+        }
+      }
+      return;
+    }
     const int nb = __builtin_amdgcn_readfirstlane(n0 + wc * 64);
     const S6D_CONST(float) *bs = (const S6D_CONST(float) *)p.bias + nb;
     const S6D_CONST(float) *cs = (const S6D_CONST(float) *)p.CS + nb;
@@ -461,6 +560,22 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   char *ep_base = nullptr;                                               // this tile's store base of the lane and the row stride in bytes
   long ep_row = 0;
   auto epilogue_qt = [&](int mt, int m0, int n0) __attribute__((always_inline)) {
+    // MI = 16: strip mt = m tiles 2 mt, 2 mt + 1.  One swap per register pair: sv[] = this lane's 32 consecutive columns of row lrow
+    float sv[32];
+    if constexpr (MI == 16) {
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc6[2 * mt][nt][r]), __float_as_uint(acc6[2 * mt + 1][nt][r]), false, false);
+          sv[4 * r + nt] = __uint_as_float(sw[0]);                       // lower lane group of the pair: column 4 r + nt
+          sv[16 + 4 * r + (nt ^ 1)] = __uint_as_float(sw[1]);            // upper one: its pairs are swapped
+        }
+    }
+    auto av = [&](int nt, int r) __attribute__((always_inline)) -> float {   // column 32 lh + 16 nt + r of this lane's row
+      if constexpr (MI == 16) return sv[16 * nt + r];
+      else return acc[mt][nt][r];
+    };
     if (EPI == 5) {
       // GELU, then this lane's 32 columns (32 h + 16 nt + r, r = 0..15: acc[mt][0][*] then acc[mt][1][*]) as one MX block: the
       // quantisation rule of s6d_layernorm_fp8 / utils/fp8.py per BLOCK -- scale 2^e with the smallest e for which amax / 2^e <= 448
@@ -509,18 +624,18 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sum += acc[mt][nt][r];
+        for (int r = 0; r < 16; ++r) sum += av(nt, r);
       const float mean = sum * (1.f / 32.f);
       float m2 = 0.f;
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float d = acc[mt][nt][r] - mean;
+          const float d = av(nt, r) - mean;
           m2 = fmaf(d, d, m2);
         }
-      const int m = m0 + wr * 128 + mt * 32 + (lane & 31);
-      const int pidx = ((n0 + wc * 64) >> 5) + (lane >> 5);
+      const int m = m0 + wr * 128 + mt * 32 + S6D_LROW;
+      const int pidx = ((n0 + wc * 64) >> 5) + S6D_LH;
       if (m < p.M) {
         p.SP[(size_t)(2 * pidx) * p.M + m] = sum;
         p.SP[(size_t)(2 * pidx + 1) * p.M + m] = m2;
@@ -534,7 +649,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
         float v[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          v[i] = acc[mt][nt][8 * k + i];
+          v[i] = av(nt, 8 * k + i);
           if ((EPI == 3 || EPI == 4)) v[i] *= ln_rs[mt];
         }
         if (EPI == 1 || EPI == 4) {
@@ -550,7 +665,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     quad_xchg4<1>(X[0], X[2]);
     quad_xchg4<1>(X[1], X[3]);
     // rows 32 mt + (lane & 28) + y of the wave's 128: ep_base (set once per tile by epilogue()) + a constant row stride
-    const int mq = m0 + wr * 128 + mt * 32 + (lane & 28);                // first row of this lane's quad
+    const int mq = m0 + wr * 128 + mt * 32 + S6D_LQ;                // first row of this lane's quad
     char *dst = ep_base + (long)(mt * 32) * ep_row;
 #pragma unroll
     for (int y = 0; y < 4; ++y) {
@@ -568,8 +683,8 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
       // store addresses of the tile, once (round 6): element (row, col) lives at C + row ldc + col, or -- column blocks of width
       // cblk stored as separate (M, cblk) matrices -- at C + ((col / cblk) M + row) cblk + col % cblk; either way the rows of one
       // column are a constant stride apart, so a strip's stores are base + (32 mt + y) * stride (was: a division per strip)
-      const int row = m0 + wr * 128 + (lane & 28);
-      const int col = n0 + wc * 64 + 32 * (lane >> 5) + 8 * (lane & 3);
+      const int row = m0 + wr * 128 + S6D_LQ;
+      const int col = n0 + wc * 64 + 32 * S6D_LH + 8 * (lane & 3);
       if (p.cblk > 0) {
         const int blk = col / p.cblk;
         ep_base = (char *)(p.C + ((size_t)blk * p.M + (size_t)row) * p.cblk + (col - blk * p.cblk));
@@ -660,6 +775,20 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     S6D_PIN(acc[2 * QM + 1][1]);                                                       \
     S6D_SETPRIO(0);                                                                    \
   } while (0)
+  // MI = 16: the 32 MFMAs of a phase, k step outer, tile inner (consecutive ones never share an accumulator)
+#define S6D_MSEG6(QM)                                                                  \
+  do {                                                                                 \
+    S6D_SETPRIO(1);                                                                    \
+    _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) S6D_PIN(wf6[nt][ks]); \
+    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                   \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                 \
+        _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                             \
+          if (S6D_GEMM_ABLATE & 2) S6D_PIN(xf6[mt][ks]);                               \
+          else acc6[4 * QM + mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf6[nt][ks], xf6[mt][ks], acc6[4 * QM + mt][nt], 0, 0, 0); \
+        }                                                                              \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) S6D_PIN(acc6[4 * QM + mt][nt]); \
+    S6D_SETPRIO(0);                                                                    \
+  } while (0)
 #ifdef HIPEMU
 #define S6D_LGKM0()
 #else
@@ -699,6 +828,16 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
       const bool more2 = g + 2 < G;
       // ---- phase A
       if (AMX && g + 1 < G) mx_issue();                                  // scale dwords of K tile g + 1, in front of this tile's DMA issues
+      if constexpr (MI == 16) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) wf6[nt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sB * kSlot + wfo6[nt][ks]);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) xf6[mt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sA * kSlot + mt * 2048 + foff6[ks]);
+      } else {
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
@@ -707,19 +846,29 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) xf[i][ks] = frag(sA, (unsigned)(i * 4096), ks);
+      }
       if (more2) {
         issue_b(0, ring(s0 + 8));                                        // B0, B1 of K tile g + 2 -> slots of A0, A1 (g - 1)
         issue_b(1, ring(s0 + 9));
       }
       S6D_LGKM0();
       S6D_BARRIER();
-      S6D_MSEG2(0);
+      if constexpr (MI == 16) S6D_MSEG6(0);
+      else S6D_MSEG2(0);
       S6D_BARRIER();
       // ---- phase B
+      if constexpr (MI == 16) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks)
+            xf6[mt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sA * kSlot + (4 + mt) * 2048 + foff6[ks]);
+      } else {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) xf[i][ks] = frag(sA, (unsigned)((2 + i) * 4096), ks);
+      }
       if (more2) {
         issue_a(0, s0);                                                  // A0, A1 of K tile g + 2 -> slots of B0, B1 (g)
         issue_a(1, s0 + 1);
@@ -729,7 +878,8 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
       }
       S6D_LGKM0();
       S6D_BARRIER();
-      S6D_MSEG2(1);
+      if constexpr (MI == 16) S6D_MSEG6(1);
+      else S6D_MSEG2(1);
       S6D_BARRIER();
       s0 = ring(s0 + 4);
       if (AMX && g + 1 < G) mx_take();                                   // K tile g + 1's scale dwords (landed: older than the counted wait above)
@@ -759,6 +909,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     }
     if (wr == 0) S6D_BARRIER();
 #undef S6D_MSEG2
+#undef S6D_MSEG6
     return;
   }
   static_assert(DT != 1 || S6D_GEMM_PH2, "the fp8 operands are wired into the two-phase main loop only");
@@ -872,11 +1023,14 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   if (wr == 0) S6D_BARRIER();                             // same barrier count for both halves
 #undef S6D_MSEG
 #undef S6D_MFMA
+#undef S6D_LROW
+#undef S6D_LH
+#undef S6D_LQ
 }
 
-template <int EPI, bool HAS_BIAS>
+template <int EPI, bool HAS_BIAS, int MI = 32>
 __global__ void __launch_bounds__(512, 2) gemm_bf16_kernel(GemmParams p) {
-  gemm_body<EPI, HAS_BIAS, 0>(p);
+  gemm_body<EPI, HAS_BIAS, 0, false, MI>(p);
 }
 template <int EPI, bool HAS_BIAS>
 __global__ void __launch_bounds__(512, 2) gemm_fp8_kernel(GemmParams p) {
@@ -913,8 +1067,11 @@ __global__ void __launch_bounds__(512, 2) gemm_f16_kernel(GemmParams p) {
 // DT (round 6): 0 = bf16, 2 = IEEE half operands and output (as gemm_body's).  Besides N % 256 == 128 this kernel now also serves the
 // plain / GELU launches whose 256 x 256 tiling would leave most CUs idle (gemm_launch: fewer than 160 tiles, e.g. the PEM ViT-B's
 // 6304 x 768 products: 75 tiles -> 150): half the work per tile, twice the tiles, the same products in the same order per element.
-template <int EPI, bool HAS_BIAS, int DT = 0>
+// MI = 16 (bf16 only): the 16x16x32 matrix instruction with gemm_body's fragment map, W row order, accumulator layout, lane-half swap
+// and epilogue arithmetic (see there), so that the two forms keep giving each other's bits under either shape.
+template <int EPI, bool HAS_BIAS, int DT = 0, int MI = 32>
 __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
+  static_assert(MI == 32 || (MI == 16 && DT == 0), "the 16x16x32 shape is wired for bf16 operands");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;       // M half / N half of the 256 x 128 tile
@@ -996,6 +1153,115 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
   f32x16 acc[4][2];
   int ct = 0, ck = 0, cm0, cn0;
   tile_mn(0, cm0, cn0);
+  // MI = 16: as gemm_body -- lane group lg owns the 16 columns from c16 of the wave's 64, register r of n tile nt = column 4 r + (nt ^ up)
+  const int lg = lane >> 4, up = lane >> 5, c16 = 32 * (lg & 1) + 16 * up;
+  // One offset register per operand (this kernel has none to spare): k step 1 is chunk + 4 = the offset with bit 6 flipped; the W row
+  // of n tile nt is row0 + (nt ^ (gp >> 1)) with row0 a multiple of 4, so bit 0 of nt flips bit 7 of the offset, bit 1 adds 256 and
+  // flips bit 0 of the swizzle key = bit 4 of the offset.
+  unsigned foff6 = 0, wfo6 = 0;
+  if constexpr (MI == 16) {
+    const int a = lane & 15, gp = a >> 2;
+    foff6 = (unsigned)(a * 128 + ((lg ^ ((a >> 1) & 7)) << 4));
+    const int row = wc * 64 + 32 * (gp & 1) + 16 * (gp >> 1) + 4 * (a & 3) + (gp >> 1);
+    wfo6 = (unsigned)(row * 128 + ((lg ^ ((row >> 1) & 7)) << 4));
+  }
+  f32x4 acc6[8][4];
+  auto init_acc6 = [&](int m0, int n0) __attribute__((always_inline)) {
+    int l6 = lane;                                                        // pinned: the lane geometry is re-derived per tile, not kept in registers
+    S6D_PIN(l6);
+    const int lane = l6, up = l6 >> 5, c16 = 32 * ((l6 >> 4) & 1) + 16 * up;
+    // register r of n tile nt: column c16 + 4 r + (nt ^ up); the pair swap of the upper lane half sits in the address (even nt reads
+    // at + up, odd nt at - up).  Pinned: per-lane offsets hoisted out of the tile loop would live through the K loop.
+    int be = n0 + wc * 64 + c16 + up, bo = n0 + wc * 64 + c16 - up;
+    S6D_PIN(be);
+    S6D_PIN(bo);
+    const float *bse = p.bias + be, *bso = p.bias + bo;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        const float b = HAS_BIAS ? ((nt & 1) ? bso[4 * r + nt] : bse[4 * r + nt]) : 0.f;
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt) acc6[mt][nt][r] = b;
+      }
+    }
+    if (EPI == 2) {
+#pragma unroll
+      for (int mt = 0; mt < 8; ++mt) {
+        const int m = min(m0 + wr * 128 + mt * 16 + (lane & 15), p.M - 1);     // rows past M: a valid address, never stored
+        const char *src = (const char *)p.R + (size_t)m * p.ldr2 + (size_t)(n0 + wc * 64 + c16) * 2;
+        const uint4 q0 = *reinterpret_cast<const uint4 *>(src), q1 = *reinterpret_cast<const uint4 *>(src + 16);
+        const unsigned rw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {                                       // dword 2 r + j: columns 4 r + {2 j, 2 j + 1}
+            const unsigned w = up ? ((rw[2 * r + j] >> 16) | (rw[2 * r + j] << 16)) : rw[2 * r + j];
+            acc6[mt][2 * j][r] += __uint_as_float(w << 16);
+            acc6[mt][2 * j + 1][r] += __uint_as_float(w & 0xffff0000u);
+          }
+        if (mt & 1) __builtin_amdgcn_sched_barrier(0);                       // two rows' loads in flight, not all eight (registers)
+      }
+    }
+  };
+  // gemm_body's epilogue for this layout: swap, statistics in ascending column order, GELU, rounding, quad transpose, 64 bytes per quad
+  auto epilogue6 = [&](int m0, int n0) __attribute__((always_inline)) {
+    int l6 = lane;                                                        // pinned: the lane geometry is re-derived per tile, not kept in registers
+    S6D_PIN(l6);
+    const int up = l6 >> 5, lrow = 16 * up + (l6 & 15), lh = (l6 >> 4) & 1, lq = 16 * up + (l6 & 12);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      float sv[32];
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc6[2 * s][nt][r]), __float_as_uint(acc6[2 * s + 1][nt][r]), false, false);
+          sv[4 * r + nt] = __uint_as_float(sw[0]);
+          sv[16 + 4 * r + (nt ^ 1)] = __uint_as_float(sw[1]);
+        }
+      if (EPI == 2 && p.SP) {
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) sum += sv[i];
+        const float mean = sum * (1.f / 32.f);
+        float m2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+          const float d = sv[i] - mean;
+          m2 = fmaf(d, d, m2);
+        }
+        const int m = m0 + wr * 128 + s * 32 + lrow;
+        const int pidx = ((n0 + wc * 64) >> 5) + lh;
+        if (m < p.M) {
+          p.SP[(size_t)(2 * pidx) * p.M + m] = sum;
+          p.SP[(size_t)(2 * pidx + 1) * p.M + m] = m2;
+        }
+      }
+      unsigned X[4][4];                                                    // [chunk of 8 columns][dword]
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = sv[8 * c + i];
+        if (EPI == 1) {
+          gelu_erf4(v);
+          gelu_erf4(v + 4);
+        }
+#pragma unroll
+        for (int d = 0; d < 4; ++d) X[c][d] = pack_out<DT>(v[2 * d], v[2 * d + 1]);
+      }
+      quad_xchg4<0>(X[0], X[1]);
+      quad_xchg4<0>(X[2], X[3]);
+      quad_xchg4<1>(X[0], X[2]);
+      quad_xchg4<1>(X[1], X[3]);
+      const int mq = m0 + wr * 128 + s * 32 + lq;
+      u16 *dst = p.C + (size_t)mq * p.ldc + (n0 + wc * 64 + 32 * lh + 8 * (l6 & 3));
+#pragma unroll
+      for (int y = 0; y < 4; ++y)
+        if (mq + y < p.M) *reinterpret_cast<uint4 *>(dst + (size_t)y * p.ldc) = make_uint4(X[y][0], X[y][1], X[y][2], X[y][3]);
+    }
+  };
 
   // EPI 2 (round 6): C = A W^T + bias + R summed in fp32 as in gemm_body -- the accumulators start at bias + residual (this lane's
   // row, its columns 32 nt + 8 qd + 4 h + e: 8 bytes per (mt, nt, qd), requested at the tile start) -- and the epilogue leaves the
@@ -1142,7 +1408,8 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
     issue_w(3);
     issue_a0(4);
   }
-  init_acc(cm0, cn0);
+  if constexpr (MI == 16) init_acc6(cm0, cn0);
+  else init_acc(cm0, cn0);
 
   int s0 = 0;                                                            // ring slot of W of K tile g: (3 g) % 5
   for (int g = 0; g < G; ++g) {
@@ -1150,6 +1417,49 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
     if (g + 1 < G) S6D_VMCNT(8); else S6D_VMCNT(0);
     __builtin_amdgcn_s_barrier();
     const int sW = s0, sA = ring5(s0 + 1 + wr);
+    if constexpr (MI == 16) {
+      bf16x8 wf6[4][2], xf6[8][2];
+      unsigned wo = wfo6, xo = foff6;                                    // pinned: the derived offsets are formed here, not kept across the loop
+      S6D_PIN(wo);
+      S6D_PIN(xo);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) wf6[nt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sW * kSlot + 256 * (nt >> 1) +
+                                                         (wo ^ (unsigned)(128 * (nt & 1) + 64 * ks + 16 * (nt >> 1))));
+#pragma unroll
+      for (int mt = 0; mt < 8; ++mt)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) xf6[mt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sA * kSlot + mt * 2048 + (xo ^ (unsigned)(64 * ks)));
+#ifndef HIPEMU
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
+      __builtin_amdgcn_s_barrier();
+      // four quarter steps (k step, four m tiles); the stream elements go out in front of the first three, as in the 32x32x16 loop
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (q == 0 && g + 1 < G) issue_a1(s0);
+        if (q == 1 && g + 2 < G) issue_w(ring5(s0 + 1));
+        if (q == 2 && g + 2 < G) issue_a0(ring5(s0 + 2));
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) {
+            const int mt = 4 * (q & 1) + i, ks = q >> 1;
+            acc6[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf6[nt][ks], xf6[mt][ks], acc6[mt][nt], 0, 0, 0);
+          }
+      }
+      s0 = ring5(s0 + 3);
+      if (++ck == p.nk) {
+        ck = 0;
+        epilogue6(cm0, cn0);
+        if (++ct < my_tiles) {
+          tile_mn(ct, cm0, cn0);
+          init_acc6(cm0, cn0);
+        }
+      }
+      continue;
+    }
     bf16x8 wf[2][4], xf[4][4];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
@@ -1193,6 +1503,10 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
 }  // namespace s6d
 
 using namespace s6d;
+
+// The library's choice of bf16 matrix-instruction shape for the eight-wave and the 256 x 128 form while neither switch is set
+// (profiles/gemm_mfma_shape.md holds the measurement that decides it).
+static constexpr int kGemmShape = 16;
 
 // Which kernel: the eight-wave 256 x 256 machine wherever N % 256 == 0 (every ViT shape: measured ahead of version 2 on all of them,
 // profiles/r02_gemm_v2_shapes.json); version 2 (two independent 256 x 128 workgroups per CU) serves N % 256 == 128.
@@ -1338,8 +1652,14 @@ static int gemm_launch(const void *A, long lda, const void *W, long ldw, const f
   p.GM = 8;                                                              // m-tiles per n-tile group of the schedule (profiles/r04_gemm_gm.txt)
   p.cblk = col_block;
   hipStream_t st = as_stream(stream);
+  // shape of the bf16 matrix instruction (s6d_set_gemm_mfma_shape): an explicit 16 / 32 holds; the library's choice is kGemmShape
+  // while the wave tile is not pinned -- with s6d_set_gemm_wave_tile(64 | 128) in force every form runs 32x32x16, the only shape the
+  // four-wave form has, so the pinned pair stays bit-comparable.  fp8 and IEEE half have one shape.
+  int mi = 32;
+  if (dt == 0 && epilogue <= 4)
+    mi = g_s6d_gemm_mfma_shape ? g_s6d_gemm_mfma_shape : (g_s6d_gemm_wave_tile == 0 ? kGemmShape : 32);
   // the four-wave form (csrc/s6d_gemm4.hip) where it applies and is selected (s6d_set_gemm_wave_tile; 0 = gemm4_default below)
-  if (impl == 1 && g_s6d_gemm_wave_tile != 64 && !x.sa_mx && gemm4_supports(p, epilogue, dt) &&
+  if (impl == 1 && g_s6d_gemm_wave_tile != 64 && mi == 32 && !x.sa_mx && gemm4_supports(p, epilogue, dt) &&
       (g_s6d_gemm_wave_tile == 128 || gemm4_default(p, epilogue, dt)))
     return gemm4_launch(p, epilogue, max_blocks, st, dt);
   if (impl == 2) {
@@ -1347,11 +1667,15 @@ static int gemm_launch(const void *A, long lda, const void *W, long ldw, const f
     int grid = p.ntiles < max_blocks ? p.ntiles : max_blocks;
     grid = (grid + 7) & ~7;
     const size_t lds = (size_t)5 * kSlot;
+#define S6D_GEMM2_LAUNCH_MI(E, HB, D, I)                                                                                \
+  do {                                                                                                                  \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm2_bf16_kernel<E, HB, D, I>),                          \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
+    hipLaunchKernelGGL((gemm2_bf16_kernel<E, HB, D, I>), dim3(grid), dim3(256), lds, st, p);                            \
+  } while (0)
 #define S6D_GEMM2_LAUNCH(E, HB, D)                                                                                      \
   do {                                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm2_bf16_kernel<E, HB, D>),                             \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-    hipLaunchKernelGGL((gemm2_bf16_kernel<E, HB, D>), dim3(grid), dim3(256), lds, st, p);                               \
+    if (D == 0 && mi == 16) S6D_GEMM2_LAUNCH_MI(E, HB, 0, 16); else S6D_GEMM2_LAUNCH_MI(E, HB, D, 32);                  \
   } while (0)
     if (dt == 2) {
       if (epilogue == 1) {
@@ -1367,17 +1691,22 @@ static int gemm_launch(const void *A, long lda, const void *W, long ldw, const f
       if (bias) S6D_GEMM2_LAUNCH(0, true, 0); else S6D_GEMM2_LAUNCH(0, false, 0);
     }
 #undef S6D_GEMM2_LAUNCH
+#undef S6D_GEMM2_LAUNCH_MI
     return launch_status();
   }
   if (max_blocks <= 0) max_blocks = 256;                                 // one persistent workgroup per CU
   int grid = p.ntiles < max_blocks ? p.ntiles : max_blocks;
   grid = (grid + 7) & ~7;                                                // whole XCD rounds
   const size_t lds = (size_t)kRing * kSlot;
+#define S6D_GEMM_LAUNCH_MI(E, HB, I)                                                                                    \
+  do {                                                                                                                  \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_bf16_kernel<E, HB, I>),                              \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
+    hipLaunchKernelGGL((gemm_bf16_kernel<E, HB, I>), dim3(grid), dim3(512), lds, st, p);                                \
+  } while (0)
 #define S6D_GEMM_LAUNCH(E, HB)                                                                                          \
   do {                                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_bf16_kernel<E, HB>),                                 \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-    hipLaunchKernelGGL((gemm_bf16_kernel<E, HB>), dim3(grid), dim3(512), lds, st, p);                                   \
+    if (mi == 16) S6D_GEMM_LAUNCH_MI(E, HB, 16); else S6D_GEMM_LAUNCH_MI(E, HB, 32);                                    \
   } while (0)
 #define S6D_GEMM8_LAUNCH(E, HB)                                                                                         \
   do {                                                                                                                  \
@@ -1438,5 +1767,6 @@ static int gemm_launch(const void *A, long lda, const void *W, long ldw, const f
     if (bias) S6D_GEMM_LAUNCH(0, true); else S6D_GEMM_LAUNCH(0, false);
   }
 #undef S6D_GEMM_LAUNCH
+#undef S6D_GEMM_LAUNCH_MI
   return launch_status();
 }

@@ -1011,6 +1011,12 @@ def set_gemm_wave_tile(columns):
     _call("s6d_set_gemm_wave_tile", int(columns))
 
 
+def set_gemm_mfma_shape(rows):
+    """Which bf16 matrix instruction the eight-wave and the 256 x 128 GEMM forms use (include/sam6d_hip.h: s6d_set_gemm_mfma_shape):
+    0 = the library's choice (16 while the wave tile is not pinned), 16 = 16x16x32, 32 = 32x32x16.  Process-wide."""
+    _call("s6d_set_gemm_mfma_shape", int(rows))
+
+
 def gemm_one_launch_rows(row_stride, elem_bytes=2):
     """Rows ONE launch of the bf16 / f16 GEMM kernels takes for an A operand of ``row_stride`` elements per row: their staging
     addresses are 32-bit byte offsets from A, so a launch stays below 2 GiB, in whole 256-row tiles.  The plain forms walk larger

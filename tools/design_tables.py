@@ -34,6 +34,7 @@ bf16 products = 0.56 of the nominal figure, at ≈ 1.7 – 2.0 GHz under the pow
 | `<3,true>` qkv, norm1 folded | a4 | MFMA | 644 GFLOP | {qkv['avg_ms']:.3f} ms (64) | {qkv['frac']:.3f} |
 | `<2,true>` proj / lin2 + residual + row statistics | a4, a5 | MFMA | 215 / 859 GFLOP | {proj['avg_ms']:.3f} / {lin2['avg_ms']:.3f} ms (64 each) | {proj['frac']:.3f} / {lin2['frac']:.3f} |
 | `gemm4_bf16_kernel` (s6d_gemm4, round 6): the four-wave form, 128 × 128 wave tiles | a4, a5 | MFMA | same shapes, same bits | selectable (`s6d_set_gemm_wave_tile(128)`): +0.5 … +4.6 % per kernel alone, −0.3 … −0.65 % in the step (`profiles/r06_gemm4.md`) | — |
+| the same eight-wave and 256 × 128 kernels on `v_mfma_f32_16x16x32_bf16` (`gemm_bf16_kernel<.,.,16>`, `gemm2_bf16_kernel<.,.,0,16>`; round 15) | a4, a5 | MFMA | same tiles, schedule and LDS bytes; 32 MFMAs of half the cycles per phase; W rows fed permuted, one lane-half swap per accumulator pair in the epilogue | **the library's choice for bf16** (`s6d_set_gemm_mfma_shape`): +2 … +3.7 % per kernel alone on qkv / lin1 / lin2, proj level; **−2.3 ms (1.2 %) in the step**, every run ahead of every run of the previous build; the same output bits on the benched data (`profiles/gemm_mfma_shape.md`) | — |
 | `attn_global64_kernel<80,8,3>` (s6d_attn_global.h; unit s6d_attn) | a4 (4 blocks) | MFMA | 4·4096²·80·16 heads·16 frames = 1374 GFLOP; 671 MB | {glb['avg_ms']:.3f} ms (8) | {glb['frac']:.3f} |
 | `attn_window16p_kernel<80,true>` (s6d_attn_win16.h) | a3–a4 (28 blocks) | HBM | 671 MB (78.6 GFLOP) | {win['avg_ms']:.3f} ms (56) | {win['frac']:.3f} of HBM |
 | `plin_kernel` (s6d_plin) | a15, a16, a20, a21 | HBM (3-term bf16 MFMA inside) | x, residual read once, y written once: 201 MB at M = 65536 | {plin['avg_ms']*1e3:.1f} µs at M = 65536 (the q / k / v and plain projections: 60 launches per step) | {plin['frac']:.2f} of HBM |
