@@ -28,7 +28,10 @@ extern "C" {
 #define S6D_ELAUNCH (-2)  /* hipLaunchKernel / hipGetLastError failure    */
 #define S6D_EUNSUPPORTED (-3)
 
-/* Bumped whenever a signature in this header changes; the loader (sam6d_amd/_lib.py) refuses a library whose
+/* Bumped whenever a signature in this header changes (a narrower accepted domain behind an unchanged signature, such as
+ * S6D_FINE_MATCH_MAX_INV_TEMP, is no such change: an older caller still binds, and is told S6D_EUNSUPPORTED; nor is a change in what a
+ * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
+ * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
 #define S6D_ABI_VERSION 130
 int s6d_version(void);
@@ -258,7 +261,8 @@ int s6d_weighted_procrustes_f32(const float *src, const float *ref, const float 
 
 /* Pose hypotheses of compute_coarse_Rt (utils/model_utils.py:216-231).
  * pts1 (B,N1,3), pts2 (B,N2,3) f32; pair (B,n_hyp,3) i32 = searchsorted() bins, decoded as
- * (i1, i2) = (pair / N2, pair % N2), clamped like the reference.  Outputs R (B,n_hyp,3,3),
+ * (i1, i2) = (pair / N2, pair % N2), clamped to [0, N1-1] x [0, N2-1] (the reference clamps the upper side, which the end bin
+ * N1 * N2 of searchsorted needs; a negative value, which searchsorted never returns, reads point 0).  Outputs R (B,n_hyp,3,3),
  * t (B,n_hyp,3), dis (B,n_hyp) = mean_i |(p1_i - t) R - p2_i|. */
 int s6d_pose_hypotheses_f32(const float *pts1, const float *pts2, const int32_t *pair, int B, int N1,
                             int N2, int n_hyp, float *R, float *t, float *dis, void *stream);
@@ -276,6 +280,7 @@ int s6d_cosine_similarity_f32(const float *f1, const float *f2, int B, int M1, i
  * sums normalised by (total + 1e-8), lower-bound search of the caller's uniforms rand_u (B,n_u) -> pair (B,n_u) i32 (flat bin
  * index i1 * (M2-1) + i2, or (M1-1)(M2-1) past the end, as torch.searchsorted) and w1 (B,M1-1) f32 (label1 > 0).
  * One workgroup per instance, the 196 x 196 distribution stays in LDS ((M1-1)(M2-1) * 4 B <= ~155 KB, M2 <= 256).
+ * |atten| <= S6D_ASSIGN_MAX_ABS_SCORE (not checked: that would take a pass over the matrix; see s6d_fine_assign_f32).
  * ref: compute_coarse_Rt, utils/model_utils.py:203-219. */
 int s6d_coarse_sample_f32(const float *atten, const float *rand_u, int B, int M1, int M2, int n_u, int32_t *pair, float *w1,
                           void *stream);
@@ -632,7 +637,16 @@ int s6d_linear_split_weight_f32(const float *w, long n, void *hi, void *lo, void
  *   w1   (B,M1-1)   1 if the row's arg-max over softmax(dim=2)*softmax(dim=1) is not the background column
  *   wsum (B,M1-1)   row sums of the masked assignment a_ij = p_ij w1_i w2_j   (i,j >= 1)
  *   pred (B,M1-1,3) (a_i / (wsum_i + 1e-6)) @ pts2
- * |atten| must stay below ~80 (it is cosine/temp = +-10): exp() is taken without a max shift.  M2 <= 2112. */
+ * |atten| <= S6D_ASSIGN_MAX_ABS_SCORE = 32 (it is cosine / temp = +-10 at the shipped temperature).  exp() is taken without a max
+ * shift and the scores are formed as p = (e / r_i)(e / c_j) in float32.  With a = max |atten|: the row's largest e is at least r_i / M2,
+ * so its e / r_i >= 1 / M2, and its e / c_j >= e^-a / (M1 e^a): the largest p of a row, the one the label is read from, is at least
+ * e^-2a / (M1 M2), a normal float (>= 1.2e-38 = e^-87.3) while 2 a + ln(M1 M2) <= 87: a <= 36.0 at 2049 x 2049, and 32 holds up to
+ * M1 M2 = 1e10.  (Smaller scores of the row may flush to 0: they lose the arg-max either way and weigh nothing in the sums.)  The
+ * sums themselves, at most 2112 e^32 = 1.7e17, are far from overflow.  Beyond the limit the kernels follow the float32 reference
+ * statements into their own underflow -- up to |atten| of about 80 they still give the float32 oracle's labels, which are then
+ * background where exact arithmetic says foreground -- and from 88.7 on e itself overflows: both WITHOUT an error, the input is
+ * not inspected.  M2 <= 2112. */
+#define S6D_ASSIGN_MAX_ABS_SCORE 32
 int s6d_fine_assign_f32(const float *atten, const float *pts2, int B, int M1, int M2, void *workspace, float *pred,
                         float *wsum, float *w1, void *stream);
 long s6d_fine_assign_workspace_bytes(int B, int M1, int M2);
@@ -640,6 +654,16 @@ long s6d_fine_assign_workspace_bytes(int B, int M1, int M2);
 /* Fine point matching, similarity + soft assignment fused: the (B, M1, M2) similarity matrix is never written.
  * f1 (B,M1,C), f2 (B,M2,C) f32 = out_proj features INCLUDING the background token at row 0 (un-normalised);
  * pts2 (B,M2-1,3) f32; inv_temp = 1 / temp.  -> pred (B,M1-1,3), wsum (B,M1-1), w1 (B,M1-1) f32 as s6d_fine_assign_f32.
+ * 0 < inv_temp <= S6D_FINE_MATCH_MAX_INV_TEMP = 25 (temp >= 0.04) and 3 inv_temp + ln max(M1, M2) <= 87: S6D_EUNSUPPORTED beyond
+ * either.  No max shift is taken: with T = inv_temp and |cos| <= 1 + 2^-16 after the split the kernel forms e = exp(T cos), e^2,
+ * the arg-max keys e^2 / c_j (rows) and e^2 / r_i (columns), and sums of up to M values of e and of e^2 / c <= e.  The keys decide:
+ * a row that is anti-correlated with every column has e = e^-T throughout while its columns' sums reach M e^T, so its keys are
+ * e^-2T / (M e^T) = e^-3T / M, and a key that leaves the normal range (1.2e-38 = e^-87.3; the multiplier flushes below) makes every
+ * key of the row 0 and the row background whatever its scores say: 3 T + ln M <= 87, T <= 26.5 at M = 2049; 25 is the round value
+ * below, good up to M = 160,000.  The other terms have room to spare there: e^2 <= e^50 = 5e21 and >= e^-50 = 2e-22, the sums at most
+ * M e^25 = 1.5e14 at M = 2049.  (At T = 40, which an earlier derivation from e^2 alone allowed, such a row came back background with
+ * no error.)
+ * Ties follow the reference: of equal largest scores the first index is the label (torch.max), at every size.
  * C = 256.  Tiles of the matrix are recomputed on the bf16 matrix cores with a hi/lo split of the normalised rows
  * (fp32-class similarities) in three sweeps: row sums, column sums + column labels, row labels + assignment.
  * ref: compute_feature_similarity, utils/model_utils.py:114-136 (called at model/fine_point_matching.py:75-80) +
@@ -647,6 +671,7 @@ long s6d_fine_assign_workspace_bytes(int B, int M1, int M2);
 int s6d_fine_match_f32(const float *f1, const float *f2, const float *pts2, int B, int M1, int M2, int C, float inv_temp,
                        void *workspace, float *pred, float *wsum, float *w1, void *stream);
 long s6d_fine_match_workspace_bytes(int B, int M1, int M2);
+#define S6D_FINE_MATCH_MAX_INV_TEMP 25
 
 /* Plain multi-head self-attention over a token sequence (no positional bias): qkv (B,N,3,nh,hd) bf16 ->
  * out (B,N,nh*hd) bf16, softmax(scale q.k) v; all N key slots LDS-resident (N <= ~500 at hd 64).  hd in {64, 80}.

@@ -151,7 +151,13 @@ def parse_header(text):
 
 
 with open(os.path.join(_HERE, "..", "include", "sam6d_hip.h")) as _f:
-    _ABI_VERSION, _PROTOTYPES = parse_header(_f.read())          # the one read of the header
+    _HEADER = _f.read()                                          # the one read of the header
+    _ABI_VERSION, _PROTOTYPES = parse_header(_HEADER)
+
+
+def header_constant(name):
+    """An integer `#define name value` of include/sam6d_hip.h (the limits of an entry point's accepted domain)."""
+    return int(re.search(r"^#define\s+" + re.escape(name) + r"\s+(-?\d+)\s*$", _HEADER, flags=re.M).group(1))
 
 
 def abi_version():

@@ -10,7 +10,7 @@
 // (between them: s6d_pose_hypotheses_f32 and s6d_min_dist_f32, csrc/s6d_pose.hip.)
 //
 // coarse_sample_kernel, one 1024-thread workgroup per instance:
-//   pass 1  e = exp(a) (|a| <= 1/temp = 10: no max shift), row sums by one wave per row, column sums as per-wave partials folded
+//   pass 1  e = exp(a) (no max shift: |a| <= S6D_ASSIGN_MAX_ABS_SCORE = 32, see the header; 1/temp = 10 as shipped), row sums by one wave per row, column sums as per-wave partials folded
 //           in wave order (deterministic)
 //   pass 2  p = (e / r_i)(e / c_j); row arg-max -> w1, column arg-max -> w2 (first index wins, as torch.max)
 //   pass 3  q = (p w1 w2)^1.5 for i, j >= 1 into LDS (196 x 196 floats = 150 KiB: the whole distribution stays on chip)

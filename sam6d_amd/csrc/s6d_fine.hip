@@ -17,9 +17,11 @@
 //   sweep A  owner = rows i >= 1 of f1, stream = all rows of f2     -> r_i
 //   sweep B  owner = rows j >= 1 of f2, stream = all rows of f1     -> c_j, w2_j            (needs r)
 //   sweep C  owner = rows i >= 1 of f1, stream = all rows of f2     -> w1_i, wsum_i, pred_i (needs r, c, w2)
-// and the background row / column sums r_0, c_0 (one owner each) come from a small VALU kernel.
+// and the background row / column sums r_0, c_0 (one owner each) come from a small kernel pair that repeats the sweeps' arithmetic
+// for that one owner (fine_bg_exp_kernel, fine_bg_sum_kernel below: the tie rule needs their bits).
 //
-// Arithmetic: |s| <= 1/temp = 10, so no max shift is needed (sums stay below 2049 e^10).  Labels and weights need fp32-class
+// Arithmetic: no max shift is taken, so 1/temp is bounded: S6D_FINE_MATCH_MAX_INV_TEMP = 25 (include/sam6d_hip.h derives it from the arg-max keys e^2 / c; the
+// shipped temp = 0.1 gives |s| <= 10 and sums below 2049 e^10).  Labels and weights need fp32-class
 // similarities (a bf16 product is off by 3e-2 in s): every normalised row is split x = hi + lo into two bf16 vectors and a tile is
 // hi.hi + lo.hi + hi.lo on v_mfma_f32_32x32x16_bf16 (48 MFMAs per 32 x 32 x 256 tile; the dropped lo.lo term is < 2^-16 of
 // a product).  log2(e) / temp is folded into the f1 side, so e = v_exp_f32(accumulator).
@@ -58,7 +60,6 @@ constexpr int FM_SIDE = 8;                 // floats per stream row in the side 
 constexpr int FM_SIDEB = FM_TILE * FM_SIDE * 4;
 constexpr int FM_NSIDE = 4;                // side-table ring: tile t's table is read one barrier interval after tile t + 2 is staged
 constexpr int FM_LDSB = 2 * FM_TILEB + FM_NSIDE * FM_SIDEB;
-constexpr int FM_BGCH = 8;                 // partial sums per background owner
 
 extern __shared__ __attribute__((aligned(16))) char fm_smem[];
 
@@ -91,48 +92,78 @@ __global__ __launch_bounds__(256) void fine_split_kernel(const float *__restrict
   reinterpret_cast<uint2 *>(dst + FM_C)[lane] = lo;
 }
 
-__device__ __forceinline__ float fm_bf(fm_u16 u) { return __uint_as_float((unsigned)u << 16); }
-
-// ---- background owners: r_0 = sum_j exp2(x1_0 . x2_j), c_0 = sum_i exp2(x1_i . x2_0), as FM_BGCH partial sums each ----------
-// grid (FM_BGCH, 2, B); which = 0: owner row 0 of xs1 against the rows of xs2 (valid < M2); which = 1: the converse
-__global__ __launch_bounds__(256) void fine_bg_kernel(const fm_u16 *__restrict__ xs1, const fm_u16 *__restrict__ xs2, int M1, int M2,
-                                                     int Mp1, int Mp2, float *__restrict__ part) {
-  __shared__ float red[4];
-  const int ch = blockIdx.x, which = blockIdx.y, b = blockIdx.z, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+// ---- background owners: r_0 = sum_j e_0j and c_0 = sum_i e_i0 WITH THE ARITHMETIC OF THE SWEEPS -----------------------------------
+// A row tied with the background column (a foreground column j whose feature row equals row 0 of f2, so that s_ij = s_i0 for
+// every i) is labelled background by the reference: torch.max returns the first index (model_utils.py:264-267).  The tie lives in
+// the keys e_ij^2 / c_j, so it survives only if c_0 has the very bits a sweep would give that column: the same matrix
+// instructions in the same order per similarity, the same v_exp_f32, and the same order of additions.  (Until round 16 the two
+// background sums came from a VALU kernel with its own dot product and eight partial sums: equal columns got sums that
+// differed in the last bits once there were more than two tiles of rows, and the tie went to the foreground.)
+//   fine_bg_exp_kernel  grid (FM_BGSPLIT, 2, B), which = 0: owner row 0 of xs1 against the rows of xs2, which = 1: the converse.
+//                       A wave takes whole stream tiles; its B operand holds the owner row in every column, the A fragments come
+//                       straight from global memory at the addresses the sweeps read through LDS; lanes 0 and 32 (column 0 of the
+//                       two halves) write e (0 on padding rows) to ev[b][which][stream row].
+//   fine_bg_sum_kernel  grid (2, B): lane h in {0, 1} adds the stream rows of accumulator half h in sweep order (tile ascending,
+//                       register ascending: rows 8 k + 4 h .. + 3), lane 0 adds the two halves and writes entry 0 of r / c.
+constexpr int FM_BGSPLIT = 4;
+__global__ __launch_bounds__(512) void fine_bg_exp_kernel(const fm_u16 *__restrict__ xs1, const fm_u16 *__restrict__ xs2, int M1, int M2,
+                                                         int Mp1, int Mp2, float *__restrict__ ev, int ldev) {
+  const int which = blockIdx.y, b = blockIdx.z, lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
+  const int wave = blockIdx.x * 8 + (threadIdx.x >> 6);
   const fm_u16 *own = which == 0 ? xs1 + (size_t)b * Mp1 * (2 * FM_C) : xs2 + (size_t)b * Mp2 * (2 * FM_C);
   const fm_u16 *str = which == 0 ? xs2 + (size_t)b * Mp2 * (2 * FM_C) : xs1 + (size_t)b * Mp1 * (2 * FM_C);
-  const int n = which == 0 ? M2 : M1;
-  float o[4];
-  {
-    const uint2 h = reinterpret_cast<const uint2 *>(own)[lane], l = reinterpret_cast<const uint2 *>(own + FM_C)[lane];
-    o[0] = fm_bf((fm_u16)h.x) + fm_bf((fm_u16)l.x);
-    o[1] = fm_bf((fm_u16)(h.x >> 16)) + fm_bf((fm_u16)(l.x >> 16));
-    o[2] = fm_bf((fm_u16)h.y) + fm_bf((fm_u16)l.y);
-    o[3] = fm_bf((fm_u16)(h.y >> 16)) + fm_bf((fm_u16)(l.y >> 16));
+  const int n = which == 0 ? M2 : M1, ntile = (which == 0 ? Mp2 : Mp1) / FM_TILE;
+  float *E = ev + ((size_t)b * 2 + which) * ldev;
+  fm_bf16x8 bh[16], bl[16];
+#pragma unroll
+  for (int ks = 0; ks < 16; ++ks) {
+    bh[ks] = *reinterpret_cast<const fm_bf16x8 *>(own + 16 * ks + 8 * half);
+    bl[ks] = *reinterpret_cast<const fm_bf16x8 *>(own + FM_C + 16 * ks + 8 * half);
   }
-  const int per = (n + FM_BGCH - 1) / FM_BGCH, j0 = ch * per, j1 = min(j0 + per, n);
-  float acc = 0.f;
-  for (int j = j0 + wave; j < j1; j += 4) {
-    const fm_u16 *r = str + (size_t)j * (2 * FM_C);
-    const uint2 h = reinterpret_cast<const uint2 *>(r)[lane], l = reinterpret_cast<const uint2 *>(r + FM_C)[lane];
-    float d = o[0] * (fm_bf((fm_u16)h.x) + fm_bf((fm_u16)l.x));
-    d = fmaf(o[1], fm_bf((fm_u16)(h.x >> 16)) + fm_bf((fm_u16)(l.x >> 16)), d);
-    d = fmaf(o[2], fm_bf((fm_u16)h.y) + fm_bf((fm_u16)l.y), d);
-    d = fmaf(o[3], fm_bf((fm_u16)(h.y >> 16)) + fm_bf((fm_u16)(l.y >> 16)), d);
-    d = wave_sum(d);
-    acc += __builtin_amdgcn_exp2f(d);
+  for (int t = wave; t < ntile; t += 8 * FM_BGSPLIT) {
+    const fm_u16 *row = str + (size_t)(t * FM_TILE + col) * (2 * FM_C);
+    fm_f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {                                 // the order of tile_mfma below
+      const fm_bf16x8 ah = *reinterpret_cast<const fm_bf16x8 *>(row + 16 * ks + 8 * half);
+      const fm_bf16x8 al = *reinterpret_cast<const fm_bf16x8 *>(row + FM_C + 16 * ks + 8 * half);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[ks], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[ks], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[ks], acc, 0, 0, 0);
+    }
+    if (col == 0) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int j = t * FM_TILE + (e & 3) + 8 * (e >> 2) + 4 * half;
+        E[j] = j < n ? __builtin_amdgcn_exp2f(acc[e]) : 0.f;
+      }
+    }
   }
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[((size_t)b * 2 + which) * FM_BGCH + ch] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__device__ __forceinline__ float fm_bg_sum(const float *part, int b, int which) {
-  const float *p = part + ((size_t)b * 2 + which) * FM_BGCH;
+__global__ __launch_bounds__(64) void fine_bg_sum_kernel(const float *__restrict__ ev, int ldev, int Mp1, int Mp2, float *__restrict__ r,
+                                                        float *__restrict__ c) {
+  const int which = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const int ntile = (which == 0 ? Mp2 : Mp1) / FM_TILE;
+  const float *E = ev + ((size_t)b * 2 + which) * ldev + 4 * (lane & 1);
   float s = 0.f;
+  if (lane < 2) {
+#pragma unroll 2
+    for (int t = 0; t < ntile; ++t) {
 #pragma unroll
-  for (int k = 0; k < FM_BGCH; ++k) s += p[k];                       // fixed order
-  return s;
+      for (int k = 0; k < 4; ++k) {
+        const float4 v = *reinterpret_cast<const float4 *>(E + t * FM_TILE + 8 * k);
+        s += v.x;
+        s += v.y;
+        s += v.z;
+        s += v.w;
+      }
+    }
+  }
+  s += __shfl_xor(s, 1);
+  if (lane == 0) (which == 0 ? r + (size_t)b * Mp1 : c + (size_t)b * Mp2)[0] = s;
 }
 
 struct FineParams {
@@ -140,10 +171,9 @@ struct FineParams {
   const fm_u16 *str;       // (B, Mps, 512) split rows of the stream side
   int Mo, Ms, Mpo, Mps;    // valid rows / padded rows of the two sides
   int B, nblk;             // owner blocks per instance = ceil((Mo - 1) / 256)
-  float *r;                // (B, Mp1): row sums, entries >= 1 (entry 0 comes from `bg`)
-  float *c;                // (B, Mp2): column sums, entries >= 1
+  float *r;                // (B, Mp1): row sums (entry 0 from fine_bg_sum_kernel)
+  float *c;                // (B, Mp2): column sums (entry 0 likewise)
   float *w2;               // (B, Mp2)
-  const float *bg;         // (B, 2, FM_BGCH) partial sums of r_0 / c_0
   const float *pts2;       // (B, M2 - 1, 3)
   float *pred, *wsum, *w1; // outputs of sweep C: (B, M1 - 1, 3), (B, M1 - 1), (B, M1 - 1)
   int ldr, ldc;            // row strides of r / c / w2 (= Mp1, Mp2)
@@ -158,13 +188,13 @@ __device__ __forceinline__ void fm_side_row(const FineParams &p, int b, int j, f
     out[0] = valid ? 1.f : 0.f;
   } else if (MODE == 1) {
     if (valid) {
-      const float r = j == 0 ? fm_bg_sum(p.bg, b, 0) : p.r[(size_t)b * p.ldr + j];
+      const float r = p.r[(size_t)b * p.ldr + j];
       out[0] = 1.f;
       out[1] = 1.0f / r;
     }
   } else {
     if (valid) {
-      const float c = j == 0 ? fm_bg_sum(p.bg, b, 1) : p.c[(size_t)b * p.ldc + j];
+      const float c = p.c[(size_t)b * p.ldc + j];
       const float ic = 1.0f / c;
       out[0] = ic;
       if (j >= 1) {
@@ -359,14 +389,15 @@ static inline long fm_pad(int M) { return ((long)M + FM_TILE - 1) / FM_TILE * FM
 
 extern "C" long s6d_fine_match_workspace_bytes(int B, int M1, int M2) {
   const long Mp1 = fm_pad(M1), Mp2 = fm_pad(M2);
-  // xs1 | xs2 (bf16 split rows)  +  r (B, Mp1) | c (B, Mp2) | w2 (B, Mp2) | bg partials (B, 2, FM_BGCH)   (floats)
-  return (long)B * (Mp1 + Mp2) * (2 * FM_C) * 2 + ((long)B * (Mp1 + 2 * Mp2) + (long)B * 2 * FM_BGCH) * 4 + 256;
+  // xs1 | xs2 (bf16 split rows)  +  r (B, Mp1) | c (B, Mp2) | w2 (B, Mp2) | background exponentials (B, 2, max(Mp1, Mp2))   (floats)
+  return (long)B * (Mp1 + Mp2) * (2 * FM_C) * 2 + ((long)B * (Mp1 + 2 * Mp2) + (long)B * 2 * (Mp1 > Mp2 ? Mp1 : Mp2)) * 4 + 256;
 }
 
 extern "C" int s6d_fine_match_f32(const float *f1, const float *f2, const float *pts2, int B, int M1, int M2, int C,
                                   float inv_temp, void *workspace, float *pred, float *wsum, float *w1, void *stream) {
   if (B < 0 || M1 < 2 || M2 < 2 || !(inv_temp > 0.f)) return S6D_EINVAL;
-  if (C != FM_C) return S6D_EUNSUPPORTED;
+  if (C != FM_C || !(inv_temp <= (float)S6D_FINE_MATCH_MAX_INV_TEMP)) return S6D_EUNSUPPORTED;
+  if (3.0f * inv_temp + logf((float)(M1 > M2 ? M1 : M2)) > 87.0f) return S6D_EUNSUPPORTED;      // the keys e^-3T / M must stay normal floats
   if (B == 0) return S6D_OK;
   if (!f1 || !f2 || !pts2 || !workspace || !pred || !wsum || !w1) return S6D_EINVAL;
   if (((uintptr_t)f1 | (uintptr_t)f2 | (uintptr_t)workspace) & 15) return S6D_EINVAL;
@@ -376,12 +407,14 @@ extern "C" int s6d_fine_match_f32(const float *f1, const float *f2, const float 
   float *r = reinterpret_cast<float *>(xs2 + (size_t)B * Mp2 * (2 * FM_C));
   float *c = r + (size_t)B * Mp1;
   float *w2 = c + (size_t)B * Mp2;
-  float *bg = w2 + (size_t)B * Mp2;
+  float *ev = w2 + (size_t)B * Mp2;
+  const int ldev = Mp1 > Mp2 ? Mp1 : Mp2;
   hipStream_t st = as_stream(stream);
   const float kLog2e = 1.4426950408889634f;
   hipLaunchKernelGGL(fine_split_kernel, dim3((Mp1 + 3) / 4, B), dim3(256), 0, st, f1, M1, Mp1, inv_temp * kLog2e, xs1);
   hipLaunchKernelGGL(fine_split_kernel, dim3((Mp2 + 3) / 4, B), dim3(256), 0, st, f2, M2, Mp2, 1.0f, xs2);
-  hipLaunchKernelGGL(fine_bg_kernel, dim3(FM_BGCH, 2, B), dim3(256), 0, st, xs1, xs2, M1, M2, Mp1, Mp2, bg);
+  hipLaunchKernelGGL(fine_bg_exp_kernel, dim3(FM_BGSPLIT, 2, B), dim3(512), 0, st, xs1, xs2, M1, M2, Mp1, Mp2, ev, ldev);
+  hipLaunchKernelGGL(fine_bg_sum_kernel, dim3(2, B), dim3(64), 0, st, ev, ldev, Mp1, Mp2, r, c);
   int rc = launch_status();
   if (rc) return rc;
   FineParams p;
@@ -389,7 +422,6 @@ extern "C" int s6d_fine_match_f32(const float *f1, const float *f2, const float 
   p.r = r;
   p.c = c;
   p.w2 = w2;
-  p.bg = bg;
   p.pts2 = pts2;
   p.pred = pred;
   p.wsum = wsum;

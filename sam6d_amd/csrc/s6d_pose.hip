@@ -41,8 +41,8 @@ __global__ void pose_hypotheses_kernel(const float *__restrict__ pts1, const flo
   for (int k = 0; k < 3; ++k) {
     const int id = pi[k];
     int i1 = id / N2, i2 = id % N2;
-    i1 = i1 > N1 - 1 ? N1 - 1 : i1;
-    i2 = i2 > N2 - 1 ? N2 - 1 : i2;
+    i1 = i1 > N1 - 1 ? N1 - 1 : (i1 < 0 ? 0 : i1);                    // the end bin N1 * N2 of searchsorted; a negative value
+    i2 = i2 > N2 - 1 ? N2 - 1 : (i2 < 0 ? 0 : i2);                    // (never produced) must not index in front of the cloud
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       p1[k][c] = (double)P1[i1 * 3 + c];

@@ -1358,8 +1358,14 @@ def geo_embedding_points(points, sigma_d, factor_a, Wd, bd, Wa, ba, div_term, ou
     return out
 
 
+# limits of the accepted domain, from the header: 1 / temp of fine_match (checked by the library: S6D_EUNSUPPORTED beyond), and the
+# largest |score| coarse_sample and fine_assign take (NOT checked by them: the caller knows it as 1 / temp)
+FINE_MATCH_MAX_INV_TEMP = _lib.header_constant("S6D_FINE_MATCH_MAX_INV_TEMP")
+ASSIGN_MAX_ABS_SCORE = _lib.header_constant("S6D_ASSIGN_MAX_ABS_SCORE")
+
+
 def fine_assign(atten, pts2):
-    """atten (B,M1,M2) f32, pts2 (B,M2-1,3) f32 -> pred (B,M1-1,3), wsum (B,M1-1), w1 (B,M1-1)."""
+    """atten (B,M1,M2) f32, |atten| <= ASSIGN_MAX_ABS_SCORE, pts2 (B,M2-1,3) f32 -> pred (B,M1-1,3), wsum (B,M1-1), w1 (B,M1-1)."""
     _chk(atten, torch.float32, "atten", 3)
     _chk(pts2, torch.float32, "pts2", 3)
     B, M1, M2 = atten.shape
@@ -1374,7 +1380,8 @@ def fine_assign(atten, pts2):
 
 def fine_match(f1, f2, pts2, temp):
     """f1 (B,M1,256), f2 (B,M2,256) f32 (background token at row 0), pts2 (B,M2-1,3) -> pred (B,M1-1,3), wsum, w1 (B,M1-1):
-    feature similarity + dual softmax + labels + normalised assignment without the (B,M1,M2) matrix."""
+    feature similarity + dual softmax + labels + normalised assignment without the (B,M1,M2) matrix.  1 / temp above
+    FINE_MATCH_MAX_INV_TEMP is refused by the library (S6D_EUNSUPPORTED -> RuntimeError)."""
     for t, nm in ((f1, "f1"), (f2, "f2"), (pts2, "pts2")):
         _chk(t, torch.float32, nm, 3)
     B, M1, C = f1.shape

@@ -72,7 +72,8 @@ class CoarsePointMatching(nn.Module):
         if rand_u is None:
             rand_u = torch.rand(B, n1 * 3, device=p1.device)
         model = end_points["model"] / (radius.reshape(-1, 1, 1) + 1e-6)
-        end_points["init_R"], end_points["init_t"] = coarse_Rt(atten, p1, p2, model, rand_u, n1, self.cfg.nproposal2)
+        end_points["init_R"], end_points["init_t"] = coarse_Rt(atten, p1, p2, model, rand_u, n1, self.cfg.nproposal2,
+                                                               max_abs_score=1.0 / self.cfg.temp)
         return end_points
 
 
@@ -182,11 +183,13 @@ class FinePointMatching(nn.Module):
         o1 = torch.cat([plinear(self, self.out_proj, f1[0].contiguous()), plinear(self, self.out_proj, f1[1])], dim=1)
         o2 = torch.cat([plinear(self, self.out_proj, f2[0].contiguous()), plinear(self, self.out_proj, f2[1])], dim=1)
         model = end_points["model"] / (radius.reshape(-1, 1, 1) + 1e-6)
-        if policy.guard("pem.FinePointMatching", cuda=o1.is_cuda, have=ops.have("fine_match"), f32=o1.dtype == torch.float32, C256=o1.shape[2] == 256):
+        if policy.guard("pem.FinePointMatching", cuda=o1.is_cuda, have=ops.have("fine_match"), f32=o1.dtype == torch.float32, C256=o1.shape[2] == 256,
+                        temp=0.0 < 1.0 / self.cfg.temp <= ops.FINE_MATCH_MAX_INV_TEMP):
             # similarity tiles are formed inside the assignment kernel: the (B,2049,2049) matrix is never written
             R, t, score = fine_Rt(None, p1, p2, model, feats=(o1, o2, self.cfg.temp))
         else:
-            R, t, score = fine_Rt(feature_similarity(o1, o2, self.cfg.temp), p1, p2, model)
+            # (a temperature below the kernels' domain: the scores reach 1 / temp, which fine_Rt needs to know to choose its path)
+            R, t, score = fine_Rt(feature_similarity(o1, o2, self.cfg.temp), p1, p2, model, max_abs_score=1.0 / self.cfg.temp)
         end_points["pred_R"] = R
         end_points["pred_t"] = t * (radius.reshape(-1, 1) + 1e-6)
         end_points["pred_pose_score"] = score

@@ -62,12 +62,13 @@ def min_dist_to_model(pts, R, t, model):
     return torch.cat(out, dim=1)
 
 
-def coarse_Rt(atten, pts1, pts2, model_pts, rand_u, n1=6000, n2=300):
-    """compute_coarse_Rt.  rand_u (B, 3*n1) are the uniform samples (drawn by the caller)."""
+def coarse_Rt(atten, pts1, pts2, model_pts, rand_u, n1=6000, n2=300, max_abs_score=None):
+    """compute_coarse_Rt.  rand_u (B, 3*n1) are the uniform samples (drawn by the caller); max_abs_score as in fine_Rt."""
     B, N1, _ = pts1.shape
     N2 = pts2.shape[1]
     if policy.guard("pem.compute_coarse_Rt", cuda=atten.is_cuda, have=ops.have("coarse_sample"), f32=atten.dtype == torch.float32,
-                    N2_le_255=N2 + 1 <= 256, lds=N1 * N2 * 4 <= 152 * 1024, n1_le_16384=n1 <= 16384):
+                    N2_le_255=N2 + 1 <= 256, lds=N1 * N2 * 4 <= 152 * 1024, n1_le_16384=n1 <= 16384,
+                    score_domain=max_abs_score is None or max_abs_score <= ops.ASSIGN_MAX_ABS_SCORE):
         # five launches: sampling head (dual softmax, labels, ^1.5, prefix sums, search) -> hypotheses -> the n2 smallest residuals
         # -> nearest-model-point scan -> scored arg-max
         pair, w1 = ops.coarse_sample(atten.contiguous(), rand_u.contiguous())
@@ -99,16 +100,20 @@ def coarse_Rt(atten, pts1, pts2, model_pts, rand_u, n1=6000, n2=300):
     return Rs[ar, best], ts[ar, best]
 
 
-def fine_Rt(atten, pts1, pts2, model_pts, dis_thres=0.15, feats=None):
+def fine_Rt(atten, pts1, pts2, model_pts, dis_thres=0.15, feats=None, max_abs_score=None):
     """compute_fine_Rt.  feats = (f1, f2, temp): the out_proj features the similarity is made of -- with them the fused kernel
-    forms similarity tiles on the fly and ``atten`` (the (B,2049,2049) matrix) may be None."""
+    forms similarity tiles on the fly and ``atten`` (the (B,2049,2049) matrix) may be None.  max_abs_score: the largest |atten| the
+    caller can produce (1 / temp for a cosine similarity), if it knows one: the assignment kernel takes exp() without a max shift
+    and does not inspect its input, so scores beyond ops.ASSIGN_MAX_ABS_SCORE go to the library statements."""
     if feats is not None and policy.guard("pem.compute_fine_Rt", cuda=feats[0].is_cuda, have=ops.have("fine_match"),
-                                          C256=feats[0].shape[2] == 256, f32=feats[0].dtype == torch.float32):
+                                          C256=feats[0].shape[2] == 256, f32=feats[0].dtype == torch.float32,
+                                          temp=0.0 < 1.0 / float(feats[2]) <= ops.FINE_MATCH_MAX_INV_TEMP):
         pred, wsum, w1 = ops.fine_match(feats[0].contiguous(), feats[1].contiguous(), pts2.contiguous(), float(feats[2]))
     elif atten is None:
         raise ValueError("fine_Rt needs the similarity matrix when the fused similarity kernel is not available")
     elif policy.guard("pem.compute_fine_Rt.assign", cuda=atten.is_cuda, have=ops.have("fine_assign"), cols=atten.shape[2] <= 2112,
-                      background_column=pts2.shape[1] == atten.shape[2] - 1):
+                      background_column=pts2.shape[1] == atten.shape[2] - 1,
+                      score_domain=max_abs_score is None or max_abs_score <= ops.ASSIGN_MAX_ABS_SCORE):
         pred, wsum, w1 = ops.fine_assign(atten.contiguous(), pts2.contiguous())
     else:
         amat, w1, _ = soft_assignment(atten)

@@ -13,7 +13,10 @@ python tools/stage_times.py --bop-eval [result.json]   the BOP pose errors (sam6
                                                      this process -- MSSD / MSPD of 256 estimates, 20,000 vertices, 1 and 315 symmetries;
                                                      the two depth renders and the pixel stage of VSD at 480 x 640 with 10 taus --
                                                      with the launches and the peak requested bytes of either branch and the floor of
-                                                     the pixel stage (quoted in profiles/bop_eval.md)"""
+                                                     the pixel stage (quoted in profiles/bop_eval.md)
+python tools/stage_times.py --fine-match-ab OTHER.so [result.json]   ops.fine_match at B = 32, 2049 x 2049 with this tree's library and with
+                                                     another build of it (the parent commit's) loaded into the same process,
+                                                     alternating, three runs each (quoted in profiles/pose_solver_margins.md)"""
 import json
 import statistics
 import sys
@@ -212,6 +215,44 @@ def render_times(path=None, rounds=5, calls=200):
         print(json.dumps(out))
 
 
+def fine_match_ab(other, path=None, rounds=3, calls=20):
+    """ops.fine_match at the benched size through two builds of the library in one process (ctypes keeps two copies of a library apart
+    when their paths differ): device-event times of alternating runs, means, the spread of the other build's own runs and whether
+    this build's mean lies within it; the labels of the two builds compared."""
+    import ctypes
+
+    from sam6d_amd import _lib, ops
+    libs = {"this": _lib.lib(), "other": ctypes.CDLL(other)}
+    assert libs["other"].s6d_version() == _lib.abi_version()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    B, M = 32, 2049
+    f1 = torch.randn(B, M, 256, generator=g, device="cuda")
+    f2 = f1[:, torch.randperm(M, generator=g, device="cuda")] + 0.4 * torch.randn(B, M, 256, generator=g, device="cuda")
+    pts2 = torch.randn(B, M - 1, 3, generator=g, device="cuda")
+    rows, outs = {"this": [], "other": []}, {}
+    try:
+        for r in range(rounds + 1):                                  # round 0 warms both builds up
+            for name in ("other", "this"):
+                _lib._lib = libs[name]
+                ms = _event_ms(lambda: ops.fine_match(f1, f2, pts2, 0.1), calls)
+                if r:
+                    rows[name].append(round(ms, 4))
+                outs[name] = ops.fine_match(f1, f2, pts2, 0.1)
+    finally:
+        _lib._lib = libs["this"]
+    mean = {k: sum(v) / len(v) for k, v in rows.items()}
+    out = {"device": torch.cuda.get_device_name(0), "B": B, "M": M, "calls_per_run": calls, "this_ms": rows["this"], "other_ms": rows["other"],
+           "this_mean_ms": round(mean["this"], 4), "other_mean_ms": round(mean["other"], 4),
+           "this_mean_within_other_runs": min(rows["other"]) <= mean["this"] <= max(rows["other"]), "this_mean_not_above_other_max": mean["this"] <= max(rows["other"]),
+           "label_differences": int((outs["this"][2] != outs["other"][2]).sum().item()),
+           "wsum_max_abs_diff": (outs["this"][1] - outs["other"][1]).abs().max().item(),
+           "pred_max_abs_diff": (outs["this"][0] - outs["other"][0]).abs().max().item()}
+    print(json.dumps(out), flush=True)
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def _peak_bytes(fn):
     """requested_bytes.all.peak of one call above what was held before it."""
     torch.cuda.synchronize()
@@ -299,6 +340,8 @@ if __name__ == "__main__":
         render_times(sys.argv[2] if len(sys.argv) > 2 else None)
     elif len(sys.argv) > 1 and sys.argv[1] == "--geo-ab":
         geo_ab(sys.argv[2] if len(sys.argv) > 2 else None)
+    elif len(sys.argv) > 2 and sys.argv[1] == "--fine-match-ab":
+        fine_match_ab(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
     elif len(sys.argv) > 1 and sys.argv[1] == "--coarse-sim-ab":
         coarse_sim_ab(sys.argv[2] if len(sys.argv) > 2 else None)
     else:
