@@ -21,7 +21,7 @@
 //   The decomposed bias  rel_h[q,ky] + rel_w[q,kx]  comes from two per-query tables
 //   T[j][q] = rel_pos[j] . q  (2S-1 entries) built with the same MFMA shape in the strip prologue.
 #pragma once
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 
 // Element type of q / k / v / P / the output.  The headers are compiled for two element types: from csrc/s6d_attn.hip for bf16 (SAM,
 // DINOv2: `bf16x8`, `f2bf` mean what they say), and from csrc/s6d_attn_f16.hip with S6D_ATTN_F16 = 1 for IEEE half (the PEM's ViT-B,
@@ -44,15 +44,9 @@
 namespace S6D_ATTN_NS {
 using namespace s6d;
 
+// bf16: bf16x8 is csrc/s6d_bf16.h's and the conversions forward to its pair; half: this namespace's own forms under the same names
 #if S6D_ATTN_F16
-typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8;
-#else
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-#endif
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef unsigned short u16;
-
-#if S6D_ATTN_F16
+typedef f16x8 bf16x8;
 __device__ __forceinline__ u16 f2bf(float f) {  // round-to-nearest-even
   union { _Float16 b; u16 u; } x;
   x.b = (_Float16)f;
@@ -64,12 +58,8 @@ __device__ __forceinline__ float bf2f(u16 h) {
   return (float)x.b;
 }
 #else
-__device__ __forceinline__ u16 f2bf(float f) {  // round-to-nearest-even (v_cvt_pk_bf16_f32 on gfx950)
-  union { __bf16 b; u16 u; } x;
-  x.b = (__bf16)f;
-  return x.u;
-}
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float(((unsigned)h) << 16); }
+__device__ __forceinline__ u16 f2bf(float f) { return bf16_bits(f); }
+__device__ __forceinline__ float bf2f(u16 h) { return bf16_value(h); }
 #endif
 
 struct AttnParams {
@@ -104,11 +94,8 @@ __device__ __forceinline__ const u16 *qkv_at(const AttnParams &p, size_t tok, in
 #define S6D_ATTN_ABLATE 0
 #endif
 constexpr int kAbl = S6D_ATTN_ABLATE;
-// K image rows whose (row >> 2 ^ row >> 3) & 1 is set keep their 16-byte chunks pairwise swapped: with an odd row stride (13 chunks)
-// the two row sets of a ds_read_b128 lane group ({0-3,12-15} reading chunk g, {4-11} reading chunk g + 1) otherwise meet on 5 of 16
-// bank slots (2-way conflict on every K fragment read).  The global kernels and the persistent window kernel store their K images
-// this way (KSWZ = true below); the all-resident window kernels do not.
-__device__ __forceinline__ int kswz(int row) { return ((row >> 2) ^ (row >> 3)) & 1; }
+// The global kernels and the persistent window kernel store their K images (13 chunks per row) chunk-swizzled -- kswz() of
+// csrc/s6d_bf16.h, KSWZ = true below; the all-resident window kernels do not.
 // S6D_G64_TIMING (probe build of the global64 and the persistent window kernel; process_tile carries two of its clock reads; writes 320 bytes BEHIND the output tensor, which tools/attn_time.py allocates): shader-clock totals per phase of attn_global64_kernel's tile loop,
 // per wave of workgroup 0: [barrier wait | DMA issue | QK^T + scale + max | exp + pack | P V]  (tools/attn_time.py prints them)
 #ifndef S6D_G64_TIMING
@@ -128,8 +115,6 @@ __device__ __forceinline__ int kswz(int row) { return ((row >> 2) ^ (row >> 3)) 
 constexpr float kLog2e = 1.4426950408889634f;
 // v_exp_f32 without the denormal-range fix-up of fast_exp2(): arguments here are <= 2^kDefer and tiny results may flush
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-#define S6D_LDS(T) __attribute__((address_space(3))) T
 // A kernel's dynamic LDS.  On the tests' host emulator (HIPEMU) it is a global array; tests/hipemu.py rewrites the declaration in .hip
 // text only, so headers that hold kernels declare it through this macro.
 #ifdef HIPEMU

@@ -112,12 +112,6 @@ __global__ __launch_bounds__(BE_THREADS) void pose_err_kernel(const float *__res
   }
 }
 
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(BE_THREADS) void vsd_counts_kernel(const float *__restrict__ depth_est, const float *__restrict__ depth_gt,
                                                                 const float *__restrict__ depth_test,
                                                                 const int *__restrict__ test_index, const float *__restrict__ cams,

@@ -54,6 +54,21 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   }
   return v;
 }
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffull), o);
+    const unsigned hi = __shfl_xor((unsigned)(v >> 32), o);
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+    v = w < v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 // erf-form GELU (nn.GELU(), approximate='none'):  x Phi(x) = relu(x) - |x| Q(|x|),  Q(z) = erfc(z / sqrt 2) / 2 = 2^P(z) with P the
 // degree-7 minimax fit of log2 Q on [0, 6] (tools/probes/gelu_fit.py; Q(6) = 1e-9: beyond it the tail is clamped, |error| < 3e-7 up
@@ -78,8 +93,8 @@ __device__ __forceinline__ float gelu_erf(float x) {
 // element instead of 10 + v_exp.  |x| stays a source modifier of the scalar instructions (the packed ones have none: a packed
 // final product would pay a v_and per element).  The lin1 + GELU epilogue is 128 evaluations per lane and tile with no matrix work
 // beside it.
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));       // (the other vector types: csrc/s6d_bf16.h)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <typename V>
 __device__ __forceinline__ V gelu_erf_poly(V z) {
   V p = __builtin_elementwise_fma(z, (V)(-1.833880219e-06f), (V)(6.155846495e-05f));
@@ -93,8 +108,8 @@ __device__ __forceinline__ V gelu_erf_poly(V z) {
 // four values: two independent packed chains, which the scheduler interleaves (a packed fp32 instruction that consumes the result
 // of the one right before it costs a wait state)
 __device__ __forceinline__ void gelu_erf4(float *x) {
-  const f32x4_t z = {fminf(fabsf(x[0]), 6.0f), fminf(fabsf(x[1]), 6.0f), fminf(fabsf(x[2]), 6.0f), fminf(fabsf(x[3]), 6.0f)};
-  const f32x4_t p = gelu_erf_poly(z);
+  const f32x4 z = {fminf(fabsf(x[0]), 6.0f), fminf(fabsf(x[1]), 6.0f), fminf(fabsf(x[2]), 6.0f), fminf(fabsf(x[3]), 6.0f)};
+  const f32x4 p = gelu_erf_poly(z);
 #pragma unroll
   for (int i = 0; i < 4; ++i) x[i] = fmaf(-fabsf(x[i]), __builtin_amdgcn_exp2f(p[i]), fmaxf(x[i], 0.f));
 }

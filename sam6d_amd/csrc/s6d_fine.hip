@@ -36,14 +36,10 @@
 //   * per-stream-row quantities (validity, 1/r, 1/c, w2/c, pts2) are staged per tile in LDS and read as broadcasts;
 //   * waves 0-3 run [matrix work of tile t, epilogue of tile t], waves 4-7 [epilogue of tile t-1, matrix work of tile t]: the two
 //     waves of a SIMD are half an iteration apart, one on the matrix pipe while the other is in its VALU epilogue.
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 
 namespace s6d {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 fm_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float fm_f32x16;
-typedef unsigned short fm_u16;
-#define FM_LDS(T) __attribute__((address_space(3))) T
 #define FM_GLOBAL(T) __attribute__((address_space(1))) T
 #ifdef HIPEMU
 #define FM_VMCNT0() hipemu::vmcnt_wait(0)
@@ -66,7 +62,7 @@ extern __shared__ __attribute__((aligned(16))) char fm_smem[];
 // ---- split: x -> normalise (F.normalize, eps 1e-12) -> * scale -> hi = bf16(x), lo = bf16(x - hi) -------------------------------
 // one wave per row; rows >= M (padding up to a whole tile) are zero
 __global__ __launch_bounds__(256) void fine_split_kernel(const float *__restrict__ f, int M, int Mp, float scale,
-                                                        fm_u16 *__restrict__ xs) {
+                                                        u16 *__restrict__ xs) {
   const int b = blockIdx.y, row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= Mp) return;
   uint2 hi = make_uint2(0u, 0u), lo = make_uint2(0u, 0u);
@@ -75,19 +71,13 @@ __global__ __launch_bounds__(256) void fine_split_kernel(const float *__restrict
     float ss = wave_sum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w);
     const float inv = scale / fmaxf(sqrtf(ss), 1e-12f);
     const float x[4] = {v.x * inv, v.y * inv, v.z * inv, v.w * inv};
-    fm_u16 h[4], l[4];
+    u16 h[4], l[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      union { __bf16 b; fm_u16 u; } a, c;
-      a.b = (__bf16)x[e];
-      c.b = (__bf16)(x[e] - (float)a.b);
-      h[e] = a.u;
-      l[e] = c.u;
-    }
+    for (int e = 0; e < 4; ++e) bf16_split(x[e], h[e], l[e]);
     hi = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
     lo = make_uint2((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16));
   }
-  fm_u16 *dst = xs + ((size_t)b * Mp + row) * (2 * FM_C);
+  u16 *dst = xs + ((size_t)b * Mp + row) * (2 * FM_C);
   reinterpret_cast<uint2 *>(dst)[lane] = hi;
   reinterpret_cast<uint2 *>(dst + FM_C)[lane] = lo;
 }
@@ -106,29 +96,29 @@ __global__ __launch_bounds__(256) void fine_split_kernel(const float *__restrict
 //   fine_bg_sum_kernel  grid (2, B): lane h in {0, 1} adds the stream rows of accumulator half h in sweep order (tile ascending,
 //                       register ascending: rows 8 k + 4 h .. + 3), lane 0 adds the two halves and writes entry 0 of r / c.
 constexpr int FM_BGSPLIT = 4;
-__global__ __launch_bounds__(512) void fine_bg_exp_kernel(const fm_u16 *__restrict__ xs1, const fm_u16 *__restrict__ xs2, int M1, int M2,
+__global__ __launch_bounds__(512) void fine_bg_exp_kernel(const u16 *__restrict__ xs1, const u16 *__restrict__ xs2, int M1, int M2,
                                                          int Mp1, int Mp2, float *__restrict__ ev, int ldev) {
   const int which = blockIdx.y, b = blockIdx.z, lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
   const int wave = blockIdx.x * 8 + (threadIdx.x >> 6);
-  const fm_u16 *own = which == 0 ? xs1 + (size_t)b * Mp1 * (2 * FM_C) : xs2 + (size_t)b * Mp2 * (2 * FM_C);
-  const fm_u16 *str = which == 0 ? xs2 + (size_t)b * Mp2 * (2 * FM_C) : xs1 + (size_t)b * Mp1 * (2 * FM_C);
+  const u16 *own = which == 0 ? xs1 + (size_t)b * Mp1 * (2 * FM_C) : xs2 + (size_t)b * Mp2 * (2 * FM_C);
+  const u16 *str = which == 0 ? xs2 + (size_t)b * Mp2 * (2 * FM_C) : xs1 + (size_t)b * Mp1 * (2 * FM_C);
   const int n = which == 0 ? M2 : M1, ntile = (which == 0 ? Mp2 : Mp1) / FM_TILE;
   float *E = ev + ((size_t)b * 2 + which) * ldev;
-  fm_bf16x8 bh[16], bl[16];
+  bf16x8 bh[16], bl[16];
 #pragma unroll
   for (int ks = 0; ks < 16; ++ks) {
-    bh[ks] = *reinterpret_cast<const fm_bf16x8 *>(own + 16 * ks + 8 * half);
-    bl[ks] = *reinterpret_cast<const fm_bf16x8 *>(own + FM_C + 16 * ks + 8 * half);
+    bh[ks] = *reinterpret_cast<const bf16x8 *>(own + 16 * ks + 8 * half);
+    bl[ks] = *reinterpret_cast<const bf16x8 *>(own + FM_C + 16 * ks + 8 * half);
   }
   for (int t = wave; t < ntile; t += 8 * FM_BGSPLIT) {
-    const fm_u16 *row = str + (size_t)(t * FM_TILE + col) * (2 * FM_C);
-    fm_f32x16 acc;
+    const u16 *row = str + (size_t)(t * FM_TILE + col) * (2 * FM_C);
+    f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {                                 // the order of tile_mfma below
-      const fm_bf16x8 ah = *reinterpret_cast<const fm_bf16x8 *>(row + 16 * ks + 8 * half);
-      const fm_bf16x8 al = *reinterpret_cast<const fm_bf16x8 *>(row + FM_C + 16 * ks + 8 * half);
+      const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(row + 16 * ks + 8 * half);
+      const bf16x8 al = *reinterpret_cast<const bf16x8 *>(row + FM_C + 16 * ks + 8 * half);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[ks], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[ks], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[ks], acc, 0, 0, 0);
@@ -167,8 +157,8 @@ __global__ __launch_bounds__(64) void fine_bg_sum_kernel(const float *__restrict
 }
 
 struct FineParams {
-  const fm_u16 *own;       // (B, Mpo, 512) split rows of the owner side
-  const fm_u16 *str;       // (B, Mps, 512) split rows of the stream side
+  const u16 *own;       // (B, Mpo, 512) split rows of the owner side
+  const u16 *str;       // (B, Mps, 512) split rows of the stream side
   int Mo, Ms, Mpo, Mps;    // valid rows / padded rows of the two sides
   int B, nblk;             // owner blocks per instance = ceil((Mo - 1) / 256)
   float *r;                // (B, Mp1): row sums (entry 0 from fine_bg_sum_kernel)
@@ -231,25 +221,25 @@ __global__ void __launch_bounds__(512, 2) fine_sweep_kernel(FineParams p) {
   const int ntile = p.Mps / FM_TILE;
 
   // ---- owner fragments: B operand of v_mfma_f32_32x32x16_bf16 = column `col`, k = 16 ks + 8 half .. + 7 ----------------------
-  fm_bf16x8 bh[16], bl[16];
+  bf16x8 bh[16], bl[16];
   {
-    const fm_u16 *src = p.own + ((size_t)b * p.Mpo + min(orow, p.Mpo - 1)) * (2 * FM_C);
+    const u16 *src = p.own + ((size_t)b * p.Mpo + min(orow, p.Mpo - 1)) * (2 * FM_C);
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
-      bh[ks] = *reinterpret_cast<const fm_bf16x8 *>(src + 16 * ks + 8 * half);
-      bl[ks] = *reinterpret_cast<const fm_bf16x8 *>(src + FM_C + 16 * ks + 8 * half);
+      bh[ks] = *reinterpret_cast<const bf16x8 *>(src + 16 * ks + 8 * half);
+      bl[ks] = *reinterpret_cast<const bf16x8 *>(src + FM_C + 16 * ks + 8 * half);
     }
   }
 
   // ---- staging: wave w fills rows 4 w .. 4 w + 3 of a tile, one 1-KiB LDS-DMA piece per row; lane = chunk POSITION in the row,
   // the chunk it fetches is position ^ (row & 15) (a permutation inside the row: the global read stays one 1-KiB line)
-  const fm_u16 *sbase = p.str + (size_t)b * p.Mps * (2 * FM_C);
+  const u16 *sbase = p.str + (size_t)b * p.Mps * (2 * FM_C);
   auto stage = [&](int t, int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = wave * 4 + i;
       const char *g = reinterpret_cast<const char *>(sbase + (size_t)(t * FM_TILE + row) * (2 * FM_C)) + ((lane ^ (row & 15)) << 4);
-      FM_LDS(char) *dst = (FM_LDS(char) *)fm_smem + buf * FM_TILEB + row * FM_ROWB;
+      S6D_LDS(char) *dst = (S6D_LDS(char) *)fm_smem + buf * FM_TILEB + row * FM_ROWB;
       __builtin_amdgcn_global_load_lds((const FM_GLOBAL(void) *)g, dst, 16, 0, 0);
     }
     if (tid < FM_TILE) {
@@ -264,17 +254,17 @@ __global__ void __launch_bounds__(512, 2) fine_sweep_kernel(FineParams p) {
   // ---- A fragment of stream row `col` for k-step ks: chunk 2 ks + half (hi), 32 + 2 ks + half (lo), at its permuted position
   const unsigned arow = (unsigned)(col * FM_ROWB);
   const unsigned asw = (unsigned)(col & 15);
-  auto afrag = [&](int buf, int chunk) __attribute__((always_inline)) -> fm_bf16x8 {
-    return *reinterpret_cast<const fm_bf16x8 *>(fm_smem + buf * FM_TILEB + arow + (((unsigned)chunk ^ asw) << 4));
+  auto afrag = [&](int buf, int chunk) __attribute__((always_inline)) -> bf16x8 {
+    return *reinterpret_cast<const bf16x8 *>(fm_smem + buf * FM_TILEB + arow + (((unsigned)chunk ^ asw) << 4));
   };
-  auto tile_mfma = [&](int buf, fm_f32x16 &acc) __attribute__((always_inline)) {
+  auto tile_mfma = [&](int buf, f32x16 &acc) __attribute__((always_inline)) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
     // fragment reads run at most 4 k-steps (8 fragments, 32 VGPRs) ahead of their MFMAs: without the fences the scheduler hoists
     // all 32 reads of the tile and spills
 #pragma unroll
     for (int kg = 0; kg < 4; ++kg) {
-      fm_bf16x8 ah[4], al[4];
+      bf16x8 ah[4], al[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         ah[k] = afrag(buf, 2 * (4 * kg + k) + half);
@@ -296,7 +286,7 @@ __global__ void __launch_bounds__(512, 2) fine_sweep_kernel(FineParams p) {
   float best = -1.f;                                                 // B, C: running arg-max key, first index wins
   int bidx = 0;
   float px = 0.f, py = 0.f, pz = 0.f;                                // C
-  auto epilogue = [&](int t, const fm_f32x16 &acc) __attribute__((always_inline)) {
+  auto epilogue = [&](int t, const f32x16 &acc) __attribute__((always_inline)) {
     const float *side = reinterpret_cast<const float *>(fm_smem + 2 * FM_TILEB + (t & (FM_NSIDE - 1)) * FM_SIDEB);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -331,7 +321,7 @@ __global__ void __launch_bounds__(512, 2) fine_sweep_kernel(FineParams p) {
   stage(0, 0);
   FM_VMCNT0();
   __syncthreads();
-  fm_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;
   for (int t = 0; t < ntile; ++t) {
@@ -402,8 +392,8 @@ extern "C" int s6d_fine_match_f32(const float *f1, const float *f2, const float 
   if (!f1 || !f2 || !pts2 || !workspace || !pred || !wsum || !w1) return S6D_EINVAL;
   if (((uintptr_t)f1 | (uintptr_t)f2 | (uintptr_t)workspace) & 15) return S6D_EINVAL;
   const int Mp1 = (int)fm_pad(M1), Mp2 = (int)fm_pad(M2);
-  fm_u16 *xs1 = reinterpret_cast<fm_u16 *>(workspace);
-  fm_u16 *xs2 = xs1 + (size_t)B * Mp1 * (2 * FM_C);
+  u16 *xs1 = reinterpret_cast<u16 *>(workspace);
+  u16 *xs2 = xs1 + (size_t)B * Mp1 * (2 * FM_C);
   float *r = reinterpret_cast<float *>(xs2 + (size_t)B * Mp2 * (2 * FM_C));
   float *c = r + (size_t)B * Mp1;
   float *w2 = c + (size_t)B * Mp2;

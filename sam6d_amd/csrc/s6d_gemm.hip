@@ -30,15 +30,11 @@
 //     v_permlane32_swap pairs the two lane halves into 16-byte row segments.
 //   * MI (template parameter of gemm_body / gemm2_bf16_kernel): the bf16 matrix instruction, 32 = 32x32x16 as described here, 16 =
 //     16x16x32 on the same schedule (see gemm_body); selected per launch (s6d_set_gemm_mfma_shape, gemm_launch).
-#include "s6d_common.h"
 #include "s6d_gemm_params.h"
 #include <stdlib.h>
 
 namespace s6d {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-#define S6D_LDS(T) __attribute__((address_space(3))) T
 #define S6D_GLOBAL(T) __attribute__((address_space(1))) T
 
 #ifdef HIPEMU
@@ -134,10 +130,7 @@ __device__ __forceinline__ int ring5(int s) { return s >= 5 ? s - 5 : s; }
 // gelu_erf(): csrc/s6d_common.h (erf-form GELU as relu(x) - |x| 2^P(|x|), 6e-6 relative)
 
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  union { __bf16 b; u16 u; } a, c;
-  a.b = (__bf16)lo;                                                     // round-to-nearest-even
-  c.b = (__bf16)hi;
-  return (unsigned)a.u | ((unsigned)c.u << 16);
+  return (unsigned)bf16_bits(lo) | ((unsigned)bf16_bits(hi) << 16);
 }
 
 // DT = 0: bf16 operands, K step 64 (4 x v_mfma_f32_32x32x16_bf16 per 32 x 32 tile and K tile).
@@ -154,7 +147,6 @@ typedef __attribute__((ext_vector_type(4))) int i32x4;
 // DT = 2 (round 3): IEEE half operands and output -- the bf16 kernel with v_mfma_f32_32x32x16_f16 and an f16 pack, everything else
 // (2-byte elements: rows, ring, swizzle, epilogue layout) shared.  The PEM's ViT-B runs on it: half's 11-bit significand keeps
 // the features within 1e-3 of the fp32 extractor's (bf16: 7.6e-3), which is what the 1e-3 mm translation bar needs.
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 __device__ __forceinline__ unsigned pack_f16(float lo, float hi) {
   union { _Float16 h; u16 u; } a, c;
   a.h = (_Float16)lo;                                                   // round-to-nearest-even
@@ -163,14 +155,13 @@ __device__ __forceinline__ unsigned pack_f16(float lo, float hi) {
 }
 // bf16: ONE v_cvt_pk_bf16_f32 per dword (round 6; the scalar conversions compile to a conversion per value and an SDWA or).  IEEE half
 // stays value by value: v_cvt_pk_f16_f32 differs from v_cvt_f16_f32 on results below the smallest normal half.
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 template <int DT>
 __device__ __forceinline__ unsigned pack_out(float lo, float hi) {
 #ifdef HIPEMU
   return DT == 2 ? pack_f16(lo, hi) : pack_bf16(lo, hi);
 #else
   if constexpr (DT == 2) return pack_f16(lo, hi);
-  else return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){lo, hi}, bf16x2_t));
+  else return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
 #endif
 }
 
@@ -185,7 +176,6 @@ __device__ __forceinline__ unsigned pack_out(float lo, float hi) {
 // EPI 5 (DT = 1): C = e4m3(GELU(A W^T + bias)) with MX scales -- in the quad-transposed accumulator layout ONE lane holds a whole
 // 32-column block of its row (columns 32 h + {0..31} of the wave's 64), so the block maximum, the scale and the 32 bytes are
 // lane-local: no exchange, two 16-byte stores and one scale byte per lane and m tile.
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 // MI (the M = N of the bf16 matrix instruction): 32 = v_mfma_f32_32x32x16_bf16 as described above; 16 = v_mfma_f32_16x16x32_bf16 on
 // the SAME tile schedule, ring, LDS image, waits and barriers (bf16 operands, two-phase loop, EPI 0 - 4 only).  What changes:
@@ -396,7 +386,6 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   // row (q = 2 nt + j).  Fetched strip by strip during the current tile's epilogue, right after the strip's stores (its 32
   // accumulator registers are free by then), and first read by init_acc of the next tile, behind the drain that the bias read
   // spends there anyway: the HBM latency of a tile that no other workgroup shares hides behind a whole epilogue.
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   u32x4 rn[4][4];
   u32x4 rn6[8][2];                                                       // MI = 16: [m tile][8-column piece] of this lane group's 16 columns
   auto load_resid = [&](int mt, int m0, int n0) __attribute__((always_inline)) {

@@ -2,11 +2,9 @@
 // csrc/s6d_gemm4.hip: the four-wave form with 128 x 128 wave tiles).  One definition: gemm_launch fills it once and hands it to
 // whichever kernel the shape selects.
 #pragma once
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 
 namespace s6d {
-
-typedef unsigned short u16;
 
 struct GemmParams {
   const u16 *A;       // (M,K) bf16, row stride lda

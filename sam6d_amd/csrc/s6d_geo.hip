@@ -14,22 +14,9 @@
 // The stage in front of it -- get_embedding_indices, transformer.py:303-332: pair distances, the three nearest neighbours of every
 // anchor, the angles -- is here too: geo_indices_kernel (points -> idx4 or -> the neighbour table) and a points-fed prologue of the
 // embedding kernels, so that no (B,N,N,.) tensor besides the embedding exists (s6d_geo_embedding_points_*).
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 
 namespace s6d {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef unsigned short u16;
-
-__device__ __forceinline__ void split_bf16(float x, u16 &hi, u16 &lo) {
-  union { __bf16 b; u16 u; } h, l;
-  h.b = (__bf16)x;
-  const float xh = __uint_as_float(((unsigned)h.u) << 16);
-  l.b = (__bf16)(x - xh);
-  hi = h.u;
-  lo = l.u;
-}
 
 // sin / cos of the fp32 product x*w (the reference's argument, transformer.py:275): two-constant Cody-Waite reduction
 // to [-pi, pi] (k = rint(a / 2pi); r = a - k*2pi_hi - k*2pi_lo, both by FMA), then the hardware sine / cosine, which take
@@ -73,17 +60,6 @@ __device__ __forceinline__ float geo_index_value(int e, float nx, float ny, floa
 constexpr int GEOIDX_MAX_N = 256;                                      // a lane keeps GEOIDX_MAX_N / 64 candidates in registers
 constexpr int GEOIDX_THREADS = 256;                                    // four waves
 constexpr int GEOIDX_ANCHORS = 16;                                     // anchors per workgroup, four per wave
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffull), o);
-    const unsigned hi = __shfl_xor((unsigned)(v >> 32), o);
-    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
-    v = w < v ? w : v;
-  }
-  return v;
-}
 
 // The three nearest neighbours of anchor n, found by ONE wave (all 64 lanes call this): lane l holds the candidates m = l + 64 j as
 // keys (bits of dist(n,m)) << 32 | m -- distances are >= +0, so the unsigned order of the keys is (distance, then index): three
@@ -192,11 +168,11 @@ constexpr int GEO_C = 256;          // hidden dim
 constexpr int GEO_ROW = 40;         // LDS row stride (bf16): 32 channels + 8 pad (80 B = 5 chunks of 16 B)
 // A ds_read_b128 lane group is {rows 0-3,12-15 reading chunk g} + {rows 4-11 reading chunk g + 1}: with any odd row stride these
 // meet on 3 of 16 bank slots (2-way conflict on every fragment read: SQ_LDS_BANK_CONFLICT was a quarter of the kernel's cycles).
-// Rows with (row >> 2 ^ row >> 3) & 1 therefore keep their chunks pairwise swapped (same fix as kswz() in csrc/s6d_attn_common.h).
+// Rows with (row >> 2 ^ row >> 3) & 1 therefore keep their chunks pairwise swapped (kswz() of csrc/s6d_bf16.h).
 #ifndef S6D_GEO_KSWZ
 #define S6D_GEO_KSWZ 1
 #endif
-__device__ __forceinline__ int geo_swz(int row) { return S6D_GEO_KSWZ ? (((row >> 2) ^ (row >> 3)) & 1) : 0; }
+__device__ __forceinline__ int geo_swz(int row) { return S6D_GEO_KSWZ ? kswz(row) : 0; }
 constexpr int GEO_PAIRS = 64;       // point pairs per workgroup
 constexpr int GEO_THREADS = 512;
 
@@ -289,8 +265,8 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed_kernel(const SRC src,
       const float av[4] = {wreg[4 + n].x, wreg[4 + n].y, wreg[4 + n].z, wreg[4 + n].w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        split_bf16(dv[e], dh.h[e], dl.h[e]);
-        split_bf16(av[e], ah.h[e], al.h[e]);
+        bf16_split(dv[e], dh.h[e], dl.h[e]);
+        bf16_split(av[e], ah.h[e], al.h[e]);
       }
       const int o = row * GEO_ROW + (((col >> 1) ^ geo_swz(row)) * 8) + (col & 1) * 4;
       *reinterpret_cast<uint2 *>(lds + OFF_WDH + o) = dh.u;
@@ -320,8 +296,8 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed_kernel(const SRC src,
         const float w = div_term[ks * 16 + item_q[n] * 4 + j];
         float sn, cs;
         fast_sincos(xval[n] * w, sn, cs);                          // same fp32 product as the reference (:275)
-        split_bf16(sn, hi.h[2 * j], lo.h[2 * j]);                  // interleaved [sin w, cos w] layout (:279-280)
-        split_bf16(cs, hi.h[2 * j + 1], lo.h[2 * j + 1]);
+        bf16_split(sn, hi.h[2 * j], lo.h[2 * j]);                  // interleaved [sin w, cos w] layout (:279-280)
+        bf16_split(cs, hi.h[2 * j + 1], lo.h[2 * j + 1]);
       }
       const int o = (item_e[n] * GEO_PAIRS + item_p[n]) * GEO_ROW + (item_q[n] ^ geo_swz(item_p[n])) * 8;
       *reinterpret_cast<uint4 *>(lds + OFF_AH + o) = hi.u;
@@ -457,8 +433,8 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const SRC src, 
       for (int j = 0; j < 4; ++j) {
         float sn, cs;
         fast_sincos(xv[e] * w[j], sn, cs);                         // same fp32 product as the reference (:275)
-        split_bf16(sn, hi.h[2 * j], lo.h[2 * j]);
-        split_bf16(cs, hi.h[2 * j + 1], lo.h[2 * j + 1]);
+        bf16_split(sn, hi.h[2 * j], lo.h[2 * j]);
+        bf16_split(cs, hi.h[2 * j + 1], lo.h[2 * j + 1]);
       }
       ah[e] = hi.v;
       al[e] = lo.v;
@@ -523,8 +499,8 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const SRC src, 
           const int j = (t & 1) * 2 + jj;
           float sn, cs;
           fast_sincos(xv[e] * wq[j], sn, cs);                      // same fp32 product as the reference (:275)
-          split_bf16(sn, nhi[e].h[2 * j], nlo[e].h[2 * j]);        // interleaved [sin w, cos w] layout (:279-280)
-          split_bf16(cs, nhi[e].h[2 * j + 1], nlo[e].h[2 * j + 1]);
+          bf16_split(sn, nhi[e].h[2 * j], nlo[e].h[2 * j]);        // interleaved [sin w, cos w] layout (:279-280)
+          bf16_split(cs, nhi[e].h[2 * j + 1], nlo[e].h[2 * j + 1]);
         }
       }
 #else

@@ -9,11 +9,9 @@
 // All GEMM-shaped work uses the exact-f32 MFMA (v_mfma_f32_16x16x4_f32: an fma chain, same numerics as
 // a scalar loop) so scores keep fp32 parity with the reference; reductions (row-max, col-max, norms,
 // non-zero counts) are epilogues of the tile that produced them -- the similarity matrices never reach HBM.
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 
 namespace s6d {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 // ------------------------------------------------------------------------------------------------
 // cosine(P queries, R references), clamp to [0,1].  One wave per 16x16 output tile.
@@ -123,16 +121,6 @@ constexpr int kPsThreads = 512;
 constexpr int kPsRowsPerWave = 32;
 constexpr int kPsLdsBytes = 2 * 2 * 256 * kPsRow * 2;   // [buffer][hi | lo][256 rows][kPsRow] bf16 = 80 KB
 
-typedef __attribute__((ext_vector_type(8))) __bf16 ps_bf16x8;
-
-__device__ __forceinline__ void ps_split(float x, unsigned short &hi, unsigned short &lo) {
-  union { __bf16 b; unsigned short u; } h, l;
-  h.b = (__bf16)x;
-  l.b = (__bf16)(x - __uint_as_float(((unsigned)h.u) << 16));
-  hi = h.u;
-  lo = l.u;
-}
-
 __global__ __launch_bounds__(kPsThreads) void patch_scores_kernel(const float *__restrict__ q,
                                                                  const float *__restrict__ refstore,
                                                                  const int *__restrict__ obj, const int *__restrict__ tmpl,
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(kPsThreads) void patch_scores_kernel(const float *_
       union { uint2 u; unsigned short h[4]; } vh, vl;
       const float v[4] = {breg[j].x, breg[j].y, breg[j].z, breg[j].w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) ps_split(v[e], vh.h[e], vl.h[e]);
+      for (int e = 0; e < 4; ++e) bf16_split(v[e], vh.h[e], vl.h[e]);
       *reinterpret_cast<uint2 *>(hi + bo[j]) = vh.u;
       *reinterpret_cast<uint2 *>(lo + bo[j]) = vl.u;
     }
@@ -197,7 +185,7 @@ __global__ __launch_bounds__(kPsThreads) void patch_scores_kernel(const float *_
   const int nk = C / 32;
   for (int ks = 0; ks < nk; ++ks) {
     // this step's A fragments (registers), then the next slice's loads take off under the MFMAs
-    union { ps_bf16x8 v; unsigned short h[8]; } ah[2], al[2];
+    union { bf16x8 v; unsigned short h[8]; } ah[2], al[2];
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
       const float v[8] = {areg[n][0].x, areg[n][0].y, areg[n][0].z, areg[n][0].w,
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(kPsThreads) void patch_scores_kernel(const float *_
       float sum = 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        ps_split(v[e], ah[n].h[e], al[n].h[e]);
+        bf16_split(v[e], ah[n].h[e], al[n].h[e]);
         sum += v[e];
       }
       qsum[n] += sum;
@@ -215,8 +203,8 @@ __global__ __launch_bounds__(kPsThreads) void patch_scores_kernel(const float *_
 #pragma unroll
     for (int t = 0; t < kMaxColTiles; ++t) {
       const int o = (t * 16 + c) * kPsRow + g * 8;
-      const ps_bf16x8 bh = *reinterpret_cast<const ps_bf16x8 *>(hi + o);
-      const ps_bf16x8 bl = *reinterpret_cast<const ps_bf16x8 *>(lo + o);
+      const bf16x8 bh = *reinterpret_cast<const bf16x8 *>(hi + o);
+      const bf16x8 bl = *reinterpret_cast<const bf16x8 *>(lo + o);
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
         acc[n][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[n].v, bh, acc[n][t], 0, 0, 0);

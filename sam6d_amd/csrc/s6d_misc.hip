@@ -19,17 +19,10 @@
 //                    302 MB per 16 frames in 390 us; this pass is one coalesced 16-byte store per thread.
 //   patchify         PatchEmbed's Conv2d with kernel = stride = p (image_encoder.py:375-395) is a GEMM over the pixels of a patch:
 //                    (B,Cin,H,W) -> (B,H/p,W/p,Cin p p) in (c, dy, dx) order, the Conv2d weight's own flattening.
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 #include "s6d_seqsum.h"
 
 namespace s6d {
-
-typedef unsigned short u16;
-__device__ __forceinline__ u16 f2bf_m(float f) {
-  union { __bf16 b; u16 u; } x;
-  x.b = (__bf16)f;
-  return x.u;
-}
 
 // in (B,3,h,w) f32 -> out (B,3,S,S) bf16 or f32; pixels outside (h,w) are 0 (F.pad after normalisation)
 template <bool BF16>
@@ -53,7 +46,7 @@ __global__ void sam_preprocess_kernel(const float *__restrict__ in, int B, int h
     if (BF16) {
       union { uint2 u; u16 hh[4]; } p;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) p.hh[e] = f2bf_m(v[e]);
+      for (int e = 0; e < 4; ++e) p.hh[e] = bf16_bits(v[e]);
       *reinterpret_cast<uint2 *>(reinterpret_cast<u16 *>(out) + o) = p.u;
     } else {
       *reinterpret_cast<float4 *>(reinterpret_cast<float *>(out) + o) = make_float4(v[0], v[1], v[2], v[3]);

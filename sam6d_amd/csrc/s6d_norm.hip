@@ -5,12 +5,15 @@
 // Under reduced precision the reference (autocast) runs LayerNorm in fp32 with a cast copy on either
 // side; here one pass reads x (and the branch output to add), writes the updated residual stream and
 // the normalised activations, with fp32 statistics.  HBM-bound: 2 reads + 2 writes of C bf16 per token.
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 
 namespace s6d {
 
-typedef unsigned short u16;
-__device__ __forceinline__ float bf2f_(u16 h) { return __uint_as_float(((unsigned)h) << 16); }
+// NOT bf16_bits of csrc/s6d_bf16.h: round-to-nearest-even by integer arithmetic on the bit pattern (v_and + v_add3_u32 per element and
+// a v_perm_b32 per pair, where bf16_bits compiles to the hardware conversion v_cvt_pk_bf16_f32).  The two agree on every finite value
+// and on the infinities and differ on NaN, which the hardware conversion keeps a NaN: here a NaN whose payload sits in the low 16
+// bits only rounds to an infinity (0x7f800001 -> 0x7f80) and one with all of the upper mantissa set carries into the sign
+// (0x7fffffff -> 0x8000, 0xffffffff -> 0x0000).  The kernels of this file are scheduled around this form; it stays.
 __device__ __forceinline__ u16 f2bf_(float f) {
   unsigned u = __float_as_uint(f);
   u += 0x7fffu + ((u >> 16) & 1u);
@@ -25,7 +28,7 @@ __device__ __forceinline__ float elem2f(u16 h) {
     c.u = h;
     return (float)c.f;
   }
-  return bf2f_(h);
+  return bf16_value(h);
 }
 template <bool F16>
 __device__ __forceinline__ u16 f2elem(float f) {
@@ -139,12 +142,12 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const u16 *__restric
       if (delta) {                                      // residual add folded in, as add_layernorm_kernel
         d.u = *reinterpret_cast<const uint4 *>(delta + row * C + ch * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a.h[e] = f2bf_(bf2f_(a.h[e]) + bf2f_(d.h[e]));
+        for (int e = 0; e < 8; ++e) a.h[e] = f2bf_(bf16_value(a.h[e]) + bf16_value(d.h[e]));
         if (x_out) *reinterpret_cast<uint4 *>(x_out + row * C + ch * 8) = a.u;
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        v[i][e] = bf2f_(a.h[e]);
+        v[i][e] = bf16_value(a.h[e]);
         sum += v[i][e];
       }
     } else {
@@ -285,7 +288,7 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const u16 *__restrict__ 
     if (ch < nchunk) a.u = *reinterpret_cast<const uint4 *>(x + row * ldx + ch * 8);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      v[i][e] = bf2f_(a.h[e]);
+      v[i][e] = bf16_value(a.h[e]);
       sum += v[i][e];
     }
   }

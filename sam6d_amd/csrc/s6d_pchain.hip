@@ -31,16 +31,10 @@
 //     ds_read_b128 lane group covers 16 distinct bank slots.  The 512-wide activation never exists as a whole: for each half,
 //     expand -> ReLU -> E -> 256 more k of the squeeze product.  h stays in registers as the second residual.
 //   * no barrier inside a product; six per strip between the stages, plus the LayerNorm reductions.
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 #include "s6d_plin_math.h"
 
 namespace s6d {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 pc_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float pc_f32x16;
-typedef unsigned short u16;
-typedef __attribute__((ext_vector_type(4))) unsigned pc_u32x4;
-typedef __attribute__((ext_vector_type(4))) float pc_f32x4;
 
 constexpr int PC_FS = 264;                                 // image row: 256 bf16 + 8 pad (528 B)
 // MT = 32-row tiles per workgroup: 2 (64 rows, 137 KB of LDS) where the rows fill the chip, 1 (32 rows, 69 KB) up to 8192 rows --
@@ -54,15 +48,6 @@ struct PcCfg {
   static constexpr int OFF_AH = 0, OFF_AL = IMG, OFF_HH = 2 * IMG, OFF_HL = 3 * IMG, LDS_ELEMS = 4 * IMG;
   static constexpr int LDS_BYTES = LDS_ELEMS * 2 + ROWS * 8 * 4;
 };
-
-__device__ __forceinline__ void pc_split(float x, u16 &hi, u16 &lo) {
-  union { __bf16 b; u16 u; } h, l;
-  h.b = (__bf16)x;
-  const float xh = __uint_as_float(((unsigned)h.u) << 16);
-  l.b = (__bf16)(x - xh);
-  hi = h.u;
-  lo = l.u;
-}
 
 struct PchainParams {
   const float *a;            // (M,256) attention output, row stride lda
@@ -100,15 +85,15 @@ __global__ __launch_bounds__(256) void pchain_kernel(PchainParams p) {
   // `prefetch` issues the first PC_PF chunks of a product's W fragments; it is called BEFORE the epilogue of the previous stage so
   // that the L2 round trip runs under the LayerNorm / image writes / barriers instead of in front of the first matrix instruction.
   constexpr int NKC = 8, PC_PF = 3;
-  pc_u32x4 wr[PC_PF][8];                                     // [chunk slot][hi: nt 0 ks 0, nt 0 ks 1, nt 1 ks 0, nt 1 ks 1 | lo: the same]
+  u32x4 wr[PC_PF][8];                                        // [chunk slot][hi: nt 0 ks 0, nt 0 ks 1, nt 1 ks 0, nt 1 ks 1 | lo: the same]
   auto gload = [&](const u16 *wh, const u16 *wl, size_t t0, size_t tn, int kc, int s) __attribute__((always_inline)) {
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const size_t o = t0 + nt * tn + (size_t)(2 * kc + ks) * 512;
-        wr[s][2 * nt + ks] = *reinterpret_cast<const pc_u32x4 *>(wh + o);
-        wr[s][4 + 2 * nt + ks] = *reinterpret_cast<const pc_u32x4 *>(wl + o);
+        wr[s][2 * nt + ks] = *reinterpret_cast<const u32x4 *>(wh + o);
+        wr[s][4 + 2 * nt + ks] = *reinterpret_cast<const u32x4 *>(wl + o);
       }
   };
   auto prefetch = [&](const u16 *wh, const u16 *wl, int k16, int r0, int k16_0) __attribute__((always_inline)) {
@@ -117,31 +102,31 @@ __global__ __launch_bounds__(256) void pchain_kernel(PchainParams p) {
     for (int s = 0; s < PC_PF; ++s) gload(wh, wl, t0, (size_t)k16 * 512, s, s);
     __builtin_amdgcn_sched_barrier(0);                       // (the scheduler otherwise sinks every load to its first use: no prefetch)
   };
-  auto gemm = [&](pc_f32x16 (&acc)[MT][2], const u16 *wh, const u16 *wl, int k16, int r0, int k16_0, int xh_off, int xl_off)
+  auto gemm = [&](f32x16 (&acc)[MT][2], const u16 *wh, const u16 *wl, int k16, int r0, int k16_0, int xh_off, int xl_off)
       __attribute__((always_inline)) {
     const size_t t0 = ((size_t)((r0 >> 5) + 2 * wave) * k16 + k16_0) * 512 + lane * 8;
     const size_t tn = (size_t)k16 * 512;                                                       // to the next n tile
 #pragma unroll
     for (int kc = 0; kc < NKC; ++kc) {
       const int s = kc % PC_PF;
-      pc_bf16x8 whf[2][2], wlf[2][2];
+      bf16x8 whf[2][2], wlf[2][2];
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          whf[nt][ks] = __builtin_bit_cast(pc_bf16x8, wr[s][2 * nt + ks]);
-          wlf[nt][ks] = __builtin_bit_cast(pc_bf16x8, wr[s][4 + 2 * nt + ks]);
+          whf[nt][ks] = __builtin_bit_cast(bf16x8, wr[s][2 * nt + ks]);
+          wlf[nt][ks] = __builtin_bit_cast(bf16x8, wr[s][4 + 2 * nt + ks]);
         }
       if (kc + PC_PF < NKC) gload(wh, wl, t0, tn, kc + PC_PF, s);   // in flight under the products of this and the next three chunks
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        pc_bf16x8 xh[MT], xl[MT];
+        bf16x8 xh[MT], xl[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           const int o = (32 * mt + fr) * PC_FS + kc * 32 + (2 * ks + fh) * 8;
-          xh[mt] = *reinterpret_cast<const pc_bf16x8 *>(lds + xh_off + o);
-          xl[mt] = *reinterpret_cast<const pc_bf16x8 *>(lds + xl_off + o);
+          xh[mt] = *reinterpret_cast<const bf16x8 *>(lds + xh_off + o);
+          xl[mt] = *reinterpret_cast<const bf16x8 *>(lds + xl_off + o);
         }
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -156,7 +141,7 @@ __global__ __launch_bounds__(256) void pchain_kernel(PchainParams p) {
   };
   const int cb = 64 * wave + 4 * fh;                        // column of register r of n tile nt: cb + 32 nt + (r & 3) + 8 (r >> 2)
   // row-wise LayerNorm of the 256 values a row's eight lanes hold, in plin_kernel's arithmetic (two passes, fixed-order sums)
-  auto layernorm = [&](pc_f32x16 (&acc)[MT][2], const float *gamma, const float *beta, float eps) __attribute__((always_inline)) {
+  auto layernorm = [&](f32x16 (&acc)[MT][2], const float *gamma, const float *beta, float eps) __attribute__((always_inline)) {
     float mean[MT], rstd[MT];
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
@@ -194,7 +179,7 @@ __global__ __launch_bounds__(256) void pchain_kernel(PchainParams p) {
       }
   };
   // the values a lane holds -> the split operand image (rows 32 mt + fr, its columns)
-  auto to_image = [&](const pc_f32x16 (&v)[MT][2], int off_hi, int off_lo) __attribute__((always_inline)) {
+  auto to_image = [&](const f32x16 (&v)[MT][2], int off_hi, int off_lo) __attribute__((always_inline)) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -203,13 +188,13 @@ __global__ __launch_bounds__(256) void pchain_kernel(PchainParams p) {
         for (int q = 0; q < 4; ++q) {
           u16 h[4], l[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) pc_split(v[mt][nt][4 * q + e], h[e], l[e]);
+          for (int e = 0; e < 4; ++e) bf16_split(v[mt][nt][4 * q + e], h[e], l[e]);
           const int o = (32 * mt + fr) * PC_FS + cb + 32 * nt + 8 * q;
           *reinterpret_cast<uint2 *>(lds + off_hi + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
           *reinterpret_cast<uint2 *>(lds + off_lo + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
         }
   };
-  auto zero = [](pc_f32x16 (&acc)[MT][2]) __attribute__((always_inline)) {
+  auto zero = [](f32x16 (&acc)[MT][2]) __attribute__((always_inline)) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -224,38 +209,38 @@ __global__ __launch_bounds__(256) void pchain_kernel(PchainParams p) {
     constexpr int TPR = 8 / MT, FPT = 32 * MT;               // threads per row, floats per thread
     const int row = tid / TPR, c0 = FPT * (tid % TPR);
     const float *src = p.a + (size_t)min(m0 + row, p.M - 1) * p.lda + c0;
-    pc_f32x4 v[FPT / 4];
+    f32x4 v[FPT / 4];
 #pragma unroll
-    for (int i = 0; i < FPT / 4; ++i) v[i] = *reinterpret_cast<const pc_f32x4 *>(src + 4 * i);
+    for (int i = 0; i < FPT / 4; ++i) v[i] = *reinterpret_cast<const f32x4 *>(src + 4 * i);
 #pragma unroll
     for (int i = 0; i < FPT / 4; i += 2) {
       u16 h[8], l[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        pc_split(v[i][e], h[e], l[e]);
-        pc_split(v[i + 1][e], h[4 + e], l[4 + e]);
+        bf16_split(v[i][e], h[e], l[e]);
+        bf16_split(v[i + 1][e], h[4 + e], l[4 + e]);
       }
       const int o = row * PC_FS + c0 + 4 * i;
-      *reinterpret_cast<pc_u32x4 *>(lds + PC_OFF_AH + o) = (pc_u32x4){pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7])};
-      *reinterpret_cast<pc_u32x4 *>(lds + PC_OFF_AL + o) = (pc_u32x4){pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7])};
+      *reinterpret_cast<u32x4 *>(lds + PC_OFF_AH + o) = (u32x4){pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7])};
+      *reinterpret_cast<u32x4 *>(lds + PC_OFF_AL + o) = (u32x4){pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7])};
     }
   }
   __builtin_amdgcn_sched_barrier(0);
   __syncthreads();
 
   // ---- stage 1: h = LN1(x + a W1^T + b1)
-  pc_f32x16 h[MT][2];
+  f32x16 h[MT][2];
   zero(h);
   gemm(h, p.w1h, p.w1l, 16, 0, 0, PC_OFF_AH, PC_OFF_AL);
   // the first residual: issued before the next product's W
-  pc_f32x4 xres[MT][2][4];
+  f32x4 xres[MT][2][4];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        xres[mt][nt][q] = *reinterpret_cast<const pc_f32x4 *>(p.x + (size_t)min(m0 + 32 * mt + fr, p.M - 1) * p.ldx + cb + 32 * nt + 8 * q);
+        xres[mt][nt][q] = *reinterpret_cast<const f32x4 *>(p.x + (size_t)min(m0 + 32 * mt + fr, p.M - 1) * p.ldx + cb + 32 * nt + 8 * q);
   prefetch(p.weh, p.wel, 16, 0, 0);
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
@@ -273,11 +258,11 @@ __global__ __launch_bounds__(256) void pchain_kernel(PchainParams p) {
   __syncthreads();                                          // H complete; every wave is past its reads of A (the reductions above)
 
   // ---- stages 2 + 3: y = LN2(h + relu(h We^T + be) Ws^T + bs), the 512 expanded columns in two halves (E lives in A's buffer)
-  pc_f32x16 y[MT][2];
+  f32x16 y[MT][2];
   zero(y);
 #pragma unroll 1
   for (int c = 0; c < 2; ++c) {
-    pc_f32x16 e2[MT][2];
+    f32x16 e2[MT][2];
     zero(e2);
     gemm(e2, p.weh, p.wel, 16, 256 * c, 0, PC_OFF_HH, PC_OFF_HL);
     prefetch(p.wsh, p.wsl, 32, 0, 16 * c);
@@ -333,7 +318,7 @@ __global__ void pchain_fragment_kernel(const u16 *__restrict__ w, int N, int K, 
   const long ts = i >> 6;
   const int k16 = K / 16, s = (int)(ts % k16), t = (int)(ts / k16);
   const u16 *src = w + (size_t)(32 * t + (lane & 31)) * K + 16 * s + 8 * (lane >> 5);
-  *reinterpret_cast<pc_u32x4 *>(out + i * 8) = *reinterpret_cast<const pc_u32x4 *>(src);
+  *reinterpret_cast<u32x4 *>(out + i * 8) = *reinterpret_cast<const u32x4 *>(src);
 }
 
 }  // namespace s6d

@@ -18,31 +18,19 @@
 // its 32-feature block -- exactly the eight values the previous layer's C tiles leave in this lane -- and the weights are
 // staged in LDS in that order (split once per workgroup), one conflict-free 16-byte read per lane and operand.
 // Layer 0 (K = 6) stays fp32 VALU.
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 
 namespace s6d {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 pe_bf16x8;
-typedef unsigned short u16;
-
 constexpr int PE_WAVES = 4;
 
-__device__ __forceinline__ void pe_split(float x, u16 &hi, u16 &lo) {       // pl_split of csrc/s6d_plin.hip
-  union { __bf16 b; u16 u; } h, l;
-  h.b = (__bf16)x;
-  const float xh = __uint_as_float(((unsigned)h.u) << 16);
-  l.b = (__bf16)(x - xh);
-  hi = h.u;
-  lo = l.u;
-}
 // the eight values of a lane's k slots -> hi / lo operands
-__device__ __forceinline__ void pe_split8(const f32x4 &a, const f32x4 &b, pe_bf16x8 &hi, pe_bf16x8 &lo) {
-  union { pe_bf16x8 v; u16 h[8]; } uh, ul;
+__device__ __forceinline__ void pe_split8(const f32x4 &a, const f32x4 &b, bf16x8 &hi, bf16x8 &lo) {
+  union { bf16x8 v; u16 h[8]; } uh, ul;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    pe_split(a[e], uh.h[e], ul.h[e]);
-    pe_split(b[e], uh.h[4 + e], ul.h[4 + e]);
+    bf16_split(a[e], uh.h[e], ul.h[e]);
+    bf16_split(b[e], uh.h[4 + e], ul.h[4 + e]);
   }
   hi = uh.v;
   lo = ul.v;
@@ -66,7 +54,7 @@ __global__ __launch_bounds__(PE_WAVES * 64, 4) void pe_group_mlp_kernel(const fl
     const int e = i & 7, ln = (i >> 3) & 63, u = i >> 9;
     const int col = (e < 4) ? 4 * (ln >> 4) + e : 16 + 4 * (ln >> 4) + (e - 4);
     u16 hi, lo;
-    pe_split(W1[(16 * u + (ln & 15)) * 32 + col], hi, lo);
+    bf16_split(W1[(16 * u + (ln & 15)) * 32 + col], hi, lo);
     sW1[((u * 2 + 0) * 64 + ln) * 8 + e] = hi;
     sW1[((u * 2 + 1) * 64 + ln) * 8 + e] = lo;
   }
@@ -74,7 +62,7 @@ __global__ __launch_bounds__(PE_WAVES * 64, 4) void pe_group_mlp_kernel(const fl
     const int e = i & 7, ln = (i >> 3) & 63, vk = i >> 9, v = vk >> 1, kb = vk & 1;
     const int col = 32 * kb + ((e < 4) ? 4 * (ln >> 4) + e : 16 + 4 * (ln >> 4) + (e - 4));
     u16 hi, lo;
-    pe_split(W2[(16 * v + (ln & 15)) * 64 + col], hi, lo);
+    bf16_split(W2[(16 * v + (ln & 15)) * 64 + col], hi, lo);
     sW2[((vk * 2 + 0) * 64 + ln) * 8 + e] = hi;
     sW2[((vk * 2 + 1) * 64 + ln) * 8 + e] = lo;
   }
@@ -83,11 +71,11 @@ __global__ __launch_bounds__(PE_WAVES * 64, 4) void pe_group_mlp_kernel(const fl
   if (tid < 64) sb1[tid] = b1[tid];
   if (tid < 128) sb2[tid] = b2[tid];
   __syncthreads();
-  auto w1op = [&](int u, int part) __attribute__((always_inline)) -> pe_bf16x8 {
-    return *reinterpret_cast<const pe_bf16x8 *>(sW1 + ((u * 2 + part) * 64 + lane) * 8);
+  auto w1op = [&](int u, int part) __attribute__((always_inline)) -> bf16x8 {
+    return *reinterpret_cast<const bf16x8 *>(sW1 + ((u * 2 + part) * 64 + lane) * 8);
   };
-  auto w2op = [&](int v, int kb, int part) __attribute__((always_inline)) -> pe_bf16x8 {
-    return *reinterpret_cast<const pe_bf16x8 *>(sW2 + (((v * 2 + kb) * 2 + part) * 64 + lane) * 8);
+  auto w2op = [&](int v, int kb, int part) __attribute__((always_inline)) -> bf16x8 {
+    return *reinterpret_cast<const bf16x8 *>(sW2 + (((v * 2 + kb) * 2 + part) * 64 + lane) * 8);
   };
 
   const long npts = (long)B * N;
@@ -120,12 +108,12 @@ __global__ __launch_bounds__(PE_WAVES * 64, 4) void pe_group_mlp_kernel(const fl
           h0[t][r] = fmaxf(a, 0.f);
         }
       // layer 1: H1^T (64 x 16) = W1 (64 x 32) H0^T in one k block; the lane's eight k slots are h0[0][0..3], h0[1][0..3]
-      pe_bf16x8 xh, xl;
+      bf16x8 xh, xl;
       pe_split8(h0[0], h0[1], xh, xl);
       f32x4 h1[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const pe_bf16x8 wh = w1op(u, 0), wl = w1op(u, 1);
+        const bf16x8 wh = w1op(u, 0), wl = w1op(u, 1);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh, acc, 0, 0, 0);                  // small terms first
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl, acc, 0, 0, 0);
@@ -134,7 +122,7 @@ __global__ __launch_bounds__(PE_WAVES * 64, 4) void pe_group_mlp_kernel(const fl
         for (int r = 0; r < 4; ++r) h1[u][r] = fmaxf(acc[r] + sb1[16 * u + g * 4 + r], 0.f);
       }
       // layer 2: H2^T (128 x 16) = W2 (128 x 64) H1^T in two k blocks (tiles 2 kb, 2 kb + 1 of h1); running max of the raw accumulators
-      pe_bf16x8 yh[2], yl[2];
+      bf16x8 yh[2], yl[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) pe_split8(h1[2 * kb], h1[2 * kb + 1], yh[kb], yl[kb]);
 #pragma unroll
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(PE_WAVES * 64, 4) void pe_group_mlp_kernel(const fl
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-          const pe_bf16x8 wh = w2op(v, kb, 0), wl = w2op(v, kb, 1);
+          const bf16x8 wh = w2op(v, kb, 0), wl = w2op(v, kb, 1);
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, yh[kb], acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, yl[kb], acc, 0, 0, 0);
         }

@@ -20,32 +20,15 @@
 // of 32: x rows are split hi / lo on the way into LDS, W arrives pre-split (bf16 hi, lo matrices made once per weight version
 // by the host wrapper); the next chunk's global loads are in flight while the current one is multiplied; 50 KB of LDS per
 // workgroup, so three workgroups share a CU and fill each other's barriers.
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 #include "s6d_plin_math.h"
 
 namespace s6d {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 pl_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float pl_f32x16;
-typedef unsigned short u16;
-typedef __attribute__((ext_vector_type(4))) unsigned pl_u32x4;
-typedef __attribute__((ext_vector_type(4))) float pl_f32x4;
-
 constexpr int PL_ROWS = 64, PL_COLS = 256, PL_KC = 32, PL_STRIDE = 40;   // LDS row: 32 bf16 + 8 pad (80 B)
 constexpr int PL_OFF_XH = 0, PL_OFF_XL = PL_OFF_XH + PL_ROWS * PL_STRIDE, PL_OFF_WH = PL_OFF_XL + PL_ROWS * PL_STRIDE,
               PL_OFF_WL = PL_OFF_WH + PL_COLS * PL_STRIDE, PL_LDS_ELEMS = PL_OFF_WL + PL_COLS * PL_STRIDE;   // 25600 elems = 50 KB
-// rows whose (row >> 2 ^ row >> 3) is odd keep their 16-byte chunk pairs swapped: with an 80-byte row stride the two row sets
-// of a ds_read_b128 lane group otherwise meet on 3 of 16 bank slots (same fix as geo_embed_kernel)
-__device__ __forceinline__ int pl_swz(int row) { return ((row >> 2) ^ (row >> 3)) & 1; }
-
-__device__ __forceinline__ void pl_split(float x, u16 &hi, u16 &lo) {
-  union { __bf16 b; u16 u; } h, l;
-  h.b = (__bf16)x;
-  const float xh = __uint_as_float(((unsigned)h.u) << 16);
-  l.b = (__bf16)(x - xh);
-  hi = h.u;
-  lo = l.u;
-}
+// (the 16-byte chunks of a row are stored swizzled: kswz() of csrc/s6d_bf16.h, 80-byte rows)
 
 struct PlinParams {
   const float *x;
@@ -71,53 +54,53 @@ __global__ __launch_bounds__(256) void plin_kernel(PlinParams p) {
   const int srow = tid >> 2, sq = tid & 3;
   const float *xsrc = p.x + (size_t)min(m0 + srow, p.M - 1) * p.ldx + sq * 8;
   const u16 *whsrc = p.wh + (size_t)(n0 + srow) * p.K + sq * 8, *wlsrc = p.wl + (size_t)(n0 + srow) * p.K + sq * 8;
-  pl_f32x4 xr0, xr1;
-  pl_u32x4 wh0, wh1, wh2, wh3, wl0, wl1, wl2, wl3;
+  f32x4 xr0, xr1;
+  u32x4 wh0, wh1, wh2, wh3, wl0, wl1, wl2, wl3;
   const size_t wj = (size_t)64 * p.K;
 #define PL_GLOAD(kc)                                                                   \
   do {                                                                                 \
-    xr0 = *reinterpret_cast<const pl_f32x4 *>(xsrc + (kc) * PL_KC);                    \
-    xr1 = *reinterpret_cast<const pl_f32x4 *>(xsrc + (kc) * PL_KC + 4);                \
-    wh0 = *reinterpret_cast<const pl_u32x4 *>(whsrc + (kc) * PL_KC);                   \
-    wh1 = *reinterpret_cast<const pl_u32x4 *>(whsrc + wj + (kc) * PL_KC);              \
-    wh2 = *reinterpret_cast<const pl_u32x4 *>(whsrc + 2 * wj + (kc) * PL_KC);          \
-    wh3 = *reinterpret_cast<const pl_u32x4 *>(whsrc + 3 * wj + (kc) * PL_KC);          \
-    wl0 = *reinterpret_cast<const pl_u32x4 *>(wlsrc + (kc) * PL_KC);                   \
-    wl1 = *reinterpret_cast<const pl_u32x4 *>(wlsrc + wj + (kc) * PL_KC);              \
-    wl2 = *reinterpret_cast<const pl_u32x4 *>(wlsrc + 2 * wj + (kc) * PL_KC);          \
-    wl3 = *reinterpret_cast<const pl_u32x4 *>(wlsrc + 3 * wj + (kc) * PL_KC);          \
+    xr0 = *reinterpret_cast<const f32x4 *>(xsrc + (kc) * PL_KC);                       \
+    xr1 = *reinterpret_cast<const f32x4 *>(xsrc + (kc) * PL_KC + 4);                   \
+    wh0 = *reinterpret_cast<const u32x4 *>(whsrc + (kc) * PL_KC);                      \
+    wh1 = *reinterpret_cast<const u32x4 *>(whsrc + wj + (kc) * PL_KC);                 \
+    wh2 = *reinterpret_cast<const u32x4 *>(whsrc + 2 * wj + (kc) * PL_KC);             \
+    wh3 = *reinterpret_cast<const u32x4 *>(whsrc + 3 * wj + (kc) * PL_KC);             \
+    wl0 = *reinterpret_cast<const u32x4 *>(wlsrc + (kc) * PL_KC);                      \
+    wl1 = *reinterpret_cast<const u32x4 *>(wlsrc + wj + (kc) * PL_KC);                 \
+    wl2 = *reinterpret_cast<const u32x4 *>(wlsrc + 2 * wj + (kc) * PL_KC);             \
+    wl3 = *reinterpret_cast<const u32x4 *>(wlsrc + 3 * wj + (kc) * PL_KC);             \
   } while (0)
-  const int ox = srow * PL_STRIDE + ((sq ^ pl_swz(srow)) * 8);
+  const int ox = srow * PL_STRIDE + ((sq ^ kswz(srow)) * 8);
   int ow[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) ow[j] = (srow + 64 * j) * PL_STRIDE + ((sq ^ pl_swz(srow + 64 * j)) * 8);
+  for (int j = 0; j < 4; ++j) ow[j] = (srow + 64 * j) * PL_STRIDE + ((sq ^ kswz(srow + 64 * j)) * 8);
   auto pack2 = [](u16 a, u16 b) -> unsigned { return (unsigned)a | ((unsigned)b << 16); };
 #define PL_LSTORE()                                                                    \
   do {                                                                                 \
     u16 h[8], l[8];                                                                    \
-    pl_split(xr0[0], h[0], l[0]); pl_split(xr0[1], h[1], l[1]); pl_split(xr0[2], h[2], l[2]); pl_split(xr0[3], h[3], l[3]); \
-    pl_split(xr1[0], h[4], l[4]); pl_split(xr1[1], h[5], l[5]); pl_split(xr1[2], h[6], l[6]); pl_split(xr1[3], h[7], l[7]); \
-    pl_u32x4 vh = {pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7])};                           \
-    pl_u32x4 vl = {pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7])};                           \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_XH + ox) = vh;                          \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_XL + ox) = vl;                          \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_WH + ow[0]) = wh0;                      \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_WH + ow[1]) = wh1;                      \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_WH + ow[2]) = wh2;                      \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_WH + ow[3]) = wh3;                      \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_WL + ow[0]) = wl0;                      \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_WL + ow[1]) = wl1;                      \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_WL + ow[2]) = wl2;                      \
-    *reinterpret_cast<pl_u32x4 *>(lds + PL_OFF_WL + ow[3]) = wl3;                      \
+    bf16_split(xr0[0], h[0], l[0]); bf16_split(xr0[1], h[1], l[1]); bf16_split(xr0[2], h[2], l[2]); bf16_split(xr0[3], h[3], l[3]); \
+    bf16_split(xr1[0], h[4], l[4]); bf16_split(xr1[1], h[5], l[5]); bf16_split(xr1[2], h[6], l[6]); bf16_split(xr1[3], h[7], l[7]); \
+    u32x4 vh = {pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7])};                              \
+    u32x4 vl = {pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7])};                              \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_XH + ox) = vh;                             \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_XL + ox) = vl;                             \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_WH + ow[0]) = wh0;                         \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_WH + ow[1]) = wh1;                         \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_WH + ow[2]) = wh2;                         \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_WH + ow[3]) = wh3;                         \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_WL + ow[0]) = wl0;                         \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_WL + ow[1]) = wl1;                         \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_WL + ow[2]) = wl2;                         \
+    *reinterpret_cast<u32x4 *>(lds + PL_OFF_WL + ow[3]) = wl3;                         \
   } while (0)
 
   // ---- fragments: lane -> row lane & 31 of the 32-row tile, 8 consecutive k at 16 ks + 8 (lane >> 5)
   const int fr = lane & 31, fh = lane >> 5;
-  auto frag = [&](int off, int row, int ks) __attribute__((always_inline)) -> pl_bf16x8 {
-    return *reinterpret_cast<const pl_bf16x8 *>(lds + off + row * PL_STRIDE + (((2 * ks + fh) ^ pl_swz(row)) * 8));
+  auto frag = [&](int off, int row, int ks) __attribute__((always_inline)) -> bf16x8 {
+    return *reinterpret_cast<const bf16x8 *>(lds + off + row * PL_STRIDE + (((2 * ks + fh) ^ kswz(row)) * 8));
   };
 
-  pl_f32x16 acc[2][2];                       // [m tile][n tile]; lane -> x row 32 mt + (lane & 31); register r -> output column
+  f32x16 acc[2][2];                       // [m tile][n tile]; lane -> x row 32 mt + (lane & 31); register r -> output column
 #pragma unroll                               //   64 wave + 32 nt + (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -134,7 +117,7 @@ __global__ __launch_bounds__(256) void plin_kernel(PlinParams p) {
     if (kc + 1 < nkc) PL_GLOAD(kc + 1);      // in flight under the products below
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      pl_bf16x8 xh[2], xl[2], wh[2], wl[2];
+      bf16x8 xh[2], xl[2], wh[2], wl[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         xh[t] = frag(PL_OFF_XH, 32 * t + fr, ks);
@@ -227,7 +210,7 @@ __global__ __launch_bounds__(256) void plin_kernel(PlinParams p) {
 // W (N,K) fp32 -> bf16 hi / lo parts (once per weight version)
 __global__ void plin_split_kernel(const float *__restrict__ w, long n, u16 *__restrict__ hi, u16 *__restrict__ lo) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) pl_split(w[i], hi[i], lo[i]);
+  if (i < n) bf16_split(w[i], hi[i], lo[i]);
 }
 
 }  // namespace s6d

@@ -100,7 +100,6 @@ __global__ void pose_hypotheses_kernel(const float *__restrict__ pts1, const flo
 // array compiled to ~10 per point (a two-wide vectorised body with scalar reads and a remainder test per pair): 300 hypotheses x 196
 // points x 1024 model points per instance were 0.47 ms per 32 instances.  Per point the arithmetic is what it was -- ex ex, then
 // fma(ey, ey, .), then fma(ez, ez, .) -- so the distances keep their bits.
-typedef float md_f32x2 __attribute__((ext_vector_type(2)));
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void transform_min_dist_kernel(
     const float *__restrict__ pts, const float *__restrict__ R, const float *__restrict__ t,
@@ -126,16 +125,16 @@ __global__ __launch_bounds__(THREADS) void transform_min_dist_kernel(
   const float x = d0 * Rp[0] + d1 * Rp[3] + d2 * Rp[6];
   const float y = d0 * Rp[1] + d1 * Rp[4] + d2 * Rp[7];
   const float z = d0 * Rp[2] + d1 * Rp[5] + d2 * Rp[8];
-  const md_f32x2 x2 = {x, x}, y2 = {y, y}, z2 = {z, z};
+  const f32x2 x2 = {x, x}, y2 = {y, y}, z2 = {z, z};
   float best = 3.4e38f;
 #pragma unroll 2
   for (int m = 0; m < Np; m += 4) {
     const float4 mx = *reinterpret_cast<const float4 *>(sx + m), my = *reinterpret_cast<const float4 *>(sy + m),
                  mz = *reinterpret_cast<const float4 *>(sz + m);
-    const md_f32x2 ex0 = x2 - (md_f32x2){mx.x, mx.y}, ex1 = x2 - (md_f32x2){mx.z, mx.w};
-    const md_f32x2 ey0 = y2 - (md_f32x2){my.x, my.y}, ey1 = y2 - (md_f32x2){my.z, my.w};
-    const md_f32x2 ez0 = z2 - (md_f32x2){mz.x, mz.y}, ez1 = z2 - (md_f32x2){mz.z, mz.w};
-    md_f32x2 e0 = ex0 * ex0, e1 = ex1 * ex1;
+    const f32x2 ex0 = x2 - (f32x2){mx.x, mx.y}, ex1 = x2 - (f32x2){mx.z, mx.w};
+    const f32x2 ey0 = y2 - (f32x2){my.x, my.y}, ey1 = y2 - (f32x2){my.z, my.w};
+    const f32x2 ez0 = z2 - (f32x2){mz.x, mz.y}, ez1 = z2 - (f32x2){mz.z, mz.w};
+    f32x2 e0 = ex0 * ex0, e1 = ex1 * ex1;
     e0 = __builtin_elementwise_fma(ey0, ey0, e0);
     e1 = __builtin_elementwise_fma(ey1, ey1, e1);
     e0 = __builtin_elementwise_fma(ez0, ez0, e0);

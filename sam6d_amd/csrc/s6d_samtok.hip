@@ -19,27 +19,16 @@
 // resident: 2.9 MB per layer) through a register ring 4 chunks deep; the activations are a bf16 row image in LDS (528-byte rows:
 // conflict-free ds_read_b128).  The 2048-wide hidden layer never exists: eight 256-column slices, each expand -> ReLU -> image ->
 // 256 more k of the squeeze product (csrc/s6d_pchain.hip's scheme).
-#include "s6d_common.h"
+#include "s6d_bf16.h"
 
 namespace s6d {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 tk_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float tk_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned tk_u32x4;
-typedef unsigned short u16;
 
 constexpr int TK_ROWS = 32, TK_C = 256, TK_XS = 264;                // image row: 256 bf16 + 8 pad (528 B)
 constexpr int TK_IMG = TK_ROWS * TK_XS;                             // elements of one image
 constexpr int TK_NIMG = 5;                                          // X0, X1, Q, K, V (pre) / X0, X1 (post)
 constexpr int TK_LDS_BYTES = TK_NIMG * TK_IMG * 2 + TK_ROWS * 8 * 4;
 
-__device__ __forceinline__ u16 tk_bf16(float x) {
-  union { __bf16 b; u16 u; } h;
-  h.b = (__bf16)x;
-  return h.u;
-}
-__device__ __forceinline__ float tk_f32(u16 h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ float tk_round(float x) { return tk_f32(tk_bf16(x)); }
+__device__ __forceinline__ float tk_round(float x) { return bf16_value(bf16_bits(x)); }
 
 struct TkLinear {             // one nn.Linear: weight (N,K) bf16 in fragment order, bias (N) f32
   const u16 *w;
@@ -96,18 +85,18 @@ extern __shared__ __attribute__((aligned(16))) char tk_smem[];
 // X: image at element offset xoff, k columns [32 kc0, 32 (kc0 + nkc)) of the image row; W: fragment order with k16 = K / 16 steps
 // per tile, the steps [k16_0, k16_0 + 2 nkc) of the tiles.
 template <int NT>
-__device__ __forceinline__ void tk_gemm(tk_f32x16 (&acc)[NT], const u16 *__restrict__ w, int k16, int tile0, int k16_0, int nkc,
+__device__ __forceinline__ void tk_gemm(f32x16 (&acc)[NT], const u16 *__restrict__ w, int k16, int tile0, int k16_0, int nkc,
                                         const u16 *lds, int xoff, int lane) {
   constexpr int PF = 4;
   const int fr = lane & 31, fh = lane >> 5;
   const size_t t0 = ((size_t)tile0 * k16 + k16_0) * 512 + lane * 8;
   const size_t tn = (size_t)k16 * 512;
-  tk_u32x4 wr[PF][2 * NT];
+  u32x4 wr[PF][2 * NT];
   auto gload = [&](int kc, int s) __attribute__((always_inline)) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) wr[s][2 * nt + ks] = *reinterpret_cast<const tk_u32x4 *>(w + t0 + nt * tn + (size_t)(2 * kc + ks) * 512);
+      for (int ks = 0; ks < 2; ++ks) wr[s][2 * nt + ks] = *reinterpret_cast<const u32x4 *>(w + t0 + nt * tn + (size_t)(2 * kc + ks) * 512);
   };
 #pragma unroll
   for (int s = 0; s < PF; ++s)
@@ -117,16 +106,16 @@ __device__ __forceinline__ void tk_gemm(tk_f32x16 (&acc)[NT], const u16 *__restr
   for (int kc = 0; kc < 8; ++kc) {
     if (kc < nkc) {
       const int s = kc % PF;
-      tk_bf16x8 wf[NT][2];
+      bf16x8 wf[NT][2];
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) wf[nt][ks] = __builtin_bit_cast(tk_bf16x8, wr[s][2 * nt + ks]);
+        for (int ks = 0; ks < 2; ++ks) wf[nt][ks] = __builtin_bit_cast(bf16x8, wr[s][2 * nt + ks]);
       if (kc + PF < nkc) gload(kc + PF, s);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const tk_bf16x8 xf = *reinterpret_cast<const tk_bf16x8 *>(lds + xoff + fr * TK_XS + kc * 32 + (2 * ks + fh) * 8);
+        const bf16x8 xf = *reinterpret_cast<const bf16x8 *>(lds + xoff + fr * TK_XS + kc * 32 + (2 * ks + fh) * 8);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[nt][ks], xf, acc[nt], 0, 0, 0);
       }
@@ -135,7 +124,7 @@ __device__ __forceinline__ void tk_gemm(tk_f32x16 (&acc)[NT], const u16 *__restr
 }
 
 template <int NT>
-__device__ __forceinline__ void tk_zero(tk_f32x16 (&acc)[NT]) {
+__device__ __forceinline__ void tk_zero(f32x16 (&acc)[NT]) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -145,7 +134,7 @@ __device__ __forceinline__ void tk_zero(tk_f32x16 (&acc)[NT]) {
 // column of register r of tile nt for a wave whose first column is c0:  c0 + 32 nt + 4 fh + (r & 3) + 8 (r >> 2)
 // acc <- round_bf16(acc + bias) (optionally ReLU first): what an autocast nn.Linear returns
 template <int NT>
-__device__ __forceinline__ void tk_bias(tk_f32x16 (&acc)[NT], const float *bias, int c0, int fh, bool relu) {
+__device__ __forceinline__ void tk_bias(f32x16 (&acc)[NT], const float *bias, int c0, int fh, bool relu) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -163,19 +152,19 @@ __device__ __forceinline__ void tk_bias(tk_f32x16 (&acc)[NT], const float *bias,
 
 // the lane's values -> a bf16 image (row fr, its columns), as 8-byte stores
 template <int NT>
-__device__ __forceinline__ void tk_to_image(const tk_f32x16 (&v)[NT], u16 *lds, int off, int c0, int fr, int fh) {
+__device__ __forceinline__ void tk_to_image(const f32x16 (&v)[NT], u16 *lds, int off, int c0, int fr, int fh) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const unsigned lo = (unsigned)tk_bf16(v[nt][4 * q]) | ((unsigned)tk_bf16(v[nt][4 * q + 1]) << 16);
-      const unsigned hi = (unsigned)tk_bf16(v[nt][4 * q + 2]) | ((unsigned)tk_bf16(v[nt][4 * q + 3]) << 16);
+      const unsigned lo = (unsigned)bf16_bits(v[nt][4 * q]) | ((unsigned)bf16_bits(v[nt][4 * q + 1]) << 16);
+      const unsigned hi = (unsigned)bf16_bits(v[nt][4 * q + 2]) | ((unsigned)bf16_bits(v[nt][4 * q + 3]) << 16);
       *reinterpret_cast<uint2 *>(lds + off + fr * TK_XS + c0 + 32 * nt + 4 * fh + 8 * q) = make_uint2(lo, hi);
     }
 }
 
 // LayerNorm over the 256 values of a row (2 tiles x 16 registers x 2 half-waves x 4 waves), two passes, fixed-order sums
-__device__ __forceinline__ void tk_layernorm(tk_f32x16 (&acc)[2], const TkNorm &n, float (*red)[8], int c0, int wave, int fr, int fh) {
+__device__ __forceinline__ void tk_layernorm(f32x16 (&acc)[2], const TkNorm &n, float (*red)[8], int c0, int wave, int fr, int fh) {
   float mean = 0.f, rstd = 0.f;
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
@@ -210,7 +199,7 @@ __device__ __forceinline__ void tk_layernorm(tk_f32x16 (&acc)[2], const TkNorm &
 
 // rows of (B,T,W) f32 tensors -> registers in the accumulator layout (the lane's row, its columns); zero for padding rows
 template <int NT>
-__device__ __forceinline__ void tk_load_rows(tk_f32x16 (&v)[NT], const float *src, int width, long row, bool valid, int c0, int fh) {
+__device__ __forceinline__ void tk_load_rows(f32x16 (&v)[NT], const float *src, int width, long row, bool valid, int c0, int fh) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -221,7 +210,7 @@ __device__ __forceinline__ void tk_load_rows(tk_f32x16 (&v)[NT], const float *sr
     }
 }
 template <int NT>
-__device__ __forceinline__ void tk_store_rows(const tk_f32x16 (&v)[NT], float *dst, int width, long row, bool valid, int c0, int fh) {
+__device__ __forceinline__ void tk_store_rows(const f32x16 (&v)[NT], float *dst, int width, long row, bool valid, int c0, int fh) {
   if (!valid) return;
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
@@ -238,35 +227,35 @@ __device__ __forceinline__ void tk_store_rows(const tk_f32x16 (&v)[NT], float *d
 template <typename F>
 __device__ __forceinline__ void tk_head_fold(const u16 *__restrict__ w, const u16 *lds, int xoff, int wave, int lane, F emit) {
   const int fr = lane & 31, fh = lane >> 5;
-  tk_u32x4 wr[2][8];
+  u32x4 wr[2][8];
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-    for (int h = 0; h < 8; ++h) wr[nt][h] = *reinterpret_cast<const tk_u32x4 *>(w + ((size_t)((2 * wave + nt) * 8 + h) * 64 + lane) * 8);
+    for (int h = 0; h < 8; ++h) wr[nt][h] = *reinterpret_cast<const u32x4 *>(w + ((size_t)((2 * wave + nt) * 8 + h) * 64 + lane) * 8);
 #pragma unroll
   for (int h = 0; h < 8; ++h) {
-    const tk_bf16x8 xf = *reinterpret_cast<const tk_bf16x8 *>(lds + xoff + fr * TK_XS + 16 * h + 8 * fh);
+    const bf16x8 xf = *reinterpret_cast<const bf16x8 *>(lds + xoff + fr * TK_XS + 16 * h + 8 * fh);
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      tk_f32x16 acc;
+      f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tk_bf16x8, wr[nt][h]), xf, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wr[nt][h]), xf, acc, 0, 0, 0);
       emit(h, nt, acc);
     }
   }
 }
 // the tile of tk_head_fold as rows of a (B,64,256) bf16 tensor: out[prompt, h*8 + tok, 64 wave + 32 nt + ...] = bf16(scale * acc)
 __device__ __forceinline__ void tk_store_fold(u16 *out, int prompt, int tok, bool prompt_ok, bool tok_ok, int h, int c0, int fh,
-                                              const tk_f32x16 &acc, float scale) {
+                                              const f32x16 &acc, float scale) {
   if (!prompt_ok) return;
   u16 *dst = out + ((size_t)prompt * 64 + h * 8 + tok) * 256 + c0 + 4 * fh;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     unsigned lo = 0, hi = 0;
     if (tok_ok) {
-      lo = (unsigned)tk_bf16(acc[4 * q] * scale) | ((unsigned)tk_bf16(acc[4 * q + 1] * scale) << 16);
-      hi = (unsigned)tk_bf16(acc[4 * q + 2] * scale) | ((unsigned)tk_bf16(acc[4 * q + 3] * scale) << 16);
+      lo = (unsigned)bf16_bits(acc[4 * q] * scale) | ((unsigned)bf16_bits(acc[4 * q + 1] * scale) << 16);
+      hi = (unsigned)bf16_bits(acc[4 * q + 2] * scale) | ((unsigned)bf16_bits(acc[4 * q + 3] * scale) << 16);
     }
     *reinterpret_cast<uint2 *>(dst + 8 * q) = make_uint2(lo, hi);
   }
@@ -284,11 +273,11 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
   const int c0 = 64 * wave;                                          // the wave's columns of a 256-wide product
 
   // x = queries (+ pe) -> X0, queries -> X1 (bf16 images; rows loaded in the accumulator layout: each lane its row's columns)
-  tk_f32x16 qv[2], pv[2];
+  f32x16 qv[2], pv[2];
   tk_load_rows<2>(qv, p.queries, TK_C, row, valid, c0, fh);
   tk_load_rows<2>(pv, p.pe, TK_C, row, valid, c0, fh);
   {
-    tk_f32x16 x[2];
+    f32x16 x[2];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
@@ -299,7 +288,7 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
   __syncthreads();
   // q, k (of x), v (of queries): bf16 results -> images
   {
-    tk_f32x16 a[2];
+    f32x16 a[2];
     tk_zero<2>(a);
     tk_gemm<2>(a, p.q.w, 16, 2 * wave, 0, 8, lds, X0, lane);
     tk_bias<2>(a, p.q.b, c0, fh, false);
@@ -325,7 +314,7 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
       float qf[32], s[8];
 #pragma unroll
       for (int d8 = 0; d8 < 4; ++d8) {
-        const tk_u32x4 v = *reinterpret_cast<const tk_u32x4 *>(lds + QI + (r0 + i) * TK_XS + h * 32 + d8 * 8);
+        const u32x4 v = *reinterpret_cast<const u32x4 *>(lds + QI + (r0 + i) * TK_XS + h * 32 + d8 * 8);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           qf[d8 * 8 + 2 * e] = __uint_as_float(v[e] << 16);
@@ -339,7 +328,7 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
         if (j < p.T) {
 #pragma unroll
           for (int d8 = 0; d8 < 4; ++d8) {
-            const tk_u32x4 v = *reinterpret_cast<const tk_u32x4 *>(lds + KI + (r0 + j) * TK_XS + h * 32 + d8 * 8);
+            const u32x4 v = *reinterpret_cast<const u32x4 *>(lds + KI + (r0 + j) * TK_XS + h * 32 + d8 * 8);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               acc = __builtin_fmaf(qf[d8 * 8 + 2 * e], __uint_as_float(v[e] << 16), acc);
@@ -364,7 +353,7 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
           const float pj = tk_round(s[j] * inv);                   // .to(v.dtype)
 #pragma unroll
           for (int d8 = 0; d8 < 4; ++d8) {
-            const tk_u32x4 v = *reinterpret_cast<const tk_u32x4 *>(lds + VI + (r0 + j) * TK_XS + h * 32 + d8 * 8);
+            const u32x4 v = *reinterpret_cast<const u32x4 *>(lds + VI + (r0 + j) * TK_XS + h * 32 + d8 * 8);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               o[d8 * 8 + 2 * e] = __builtin_fmaf(pj, __uint_as_float(v[e] << 16), o[d8 * 8 + 2 * e]);
@@ -377,15 +366,15 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
     // attention output (bf16) -> X0 (its readers, the q / k products, are behind the barrier above)
 #pragma unroll
     for (int d8 = 0; d8 < 4; ++d8) {
-      tk_u32x4 v;
+      u32x4 v;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (unsigned)tk_bf16(o[d8 * 8 + 2 * e]) | ((unsigned)tk_bf16(o[d8 * 8 + 2 * e + 1]) << 16);
-      *reinterpret_cast<tk_u32x4 *>(lds + X0 + (r0 + i) * TK_XS + h * 32 + d8 * 8) = v;
+      for (int e = 0; e < 4; ++e) v[e] = (unsigned)bf16_bits(o[d8 * 8 + 2 * e]) | ((unsigned)bf16_bits(o[d8 * 8 + 2 * e + 1]) << 16);
+      *reinterpret_cast<u32x4 *>(lds + X0 + (r0 + i) * TK_XS + h * 32 + d8 * 8) = v;
     }
   }
   __syncthreads();
   // out_proj, residual (later layers), norm1
-  tk_f32x16 q1[2];
+  f32x16 q1[2];
   tk_zero<2>(q1);
   tk_gemm<2>(q1, p.o.w, 16, 2 * wave, 0, 8, lds, X0, lane);
   tk_bias<2>(q1, p.o.b, c0, fh, false);
@@ -399,7 +388,7 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
   tk_store_rows<2>(q1, p.q1_out, TK_C, row, valid, c0, fh);
   // token->image queries: q_proj(q1 + pe)
   {
-    tk_f32x16 x[2];
+    f32x16 x[2];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
@@ -407,7 +396,7 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
     tk_to_image<2>(x, lds, X1, c0, fr, fh);                          // (X1's reader, the v product, is behind two barriers)
   }
   __syncthreads();
-  tk_f32x16 qp[1];
+  f32x16 qp[1];
   tk_zero<1>(qp);
   tk_gemm<1>(qp, p.q2.w, 16, wave, 0, 8, lds, X1, lane);
   tk_bias<1>(qp, p.q2.b, 32 * wave, fh, false);
@@ -418,7 +407,7 @@ __global__ __launch_bounds__(256) void samtok_pre_kernel(SamtokPre p) {
     tk_to_image<1>(qp, lds, X0, 32 * wave, fr, fh);
     __syncthreads();
     const bool pok = prompt < p.B, tok_ok = tok < p.T;
-    tk_head_fold(p.wkfold, lds, X0, wave, lane, [&](int h, int nt, const tk_f32x16 &acc) __attribute__((always_inline)) {
+    tk_head_fold(p.wkfold, lds, X0, wave, lane, [&](int h, int nt, const f32x16 &acc) __attribute__((always_inline)) {
       tk_store_fold(p.qfold_out, prompt, tok, pok, tok_ok, h, 64 * wave + 32 * nt, fh, acc, p.fold_scale);
     });
   }
@@ -437,12 +426,12 @@ __global__ __launch_bounds__(256) void samtok_post_kernel(SamtokPost p) {
 
   // attention output (B,T,128) -> X0 columns [0, 128): wave w writes the 32 columns [32 w, 32 w + 32) of its rows
   {
-    tk_f32x16 a[1];
+    f32x16 a[1];
     if (p.y) {
       // ... made here from the attention core's raw result: the 32 columns of wave w are heads 2 w and 2 w + 1; head h multiplies ITS
       // rows y[b, h*8 + t, :] (K = 256, fp32 -> bf16 hi + lo parts: two instructions per k step keep y to 2^-17) by W_v's 32-row tile
       // w, of which its own 16 rows are kept (registers 0-7 for the even head, 8-15 for the odd one)
-      tk_f32x16 acc[2];
+      f32x16 acc[2];
       tk_zero<2>(acc);
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
@@ -457,16 +446,16 @@ __global__ __launch_bounds__(256) void samtok_post_kernel(SamtokPost p) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) {
-          const tk_u32x4 wv = *reinterpret_cast<const tk_u32x4 *>(p.wvfold + ((size_t)(wave * 16 + ks) * 64 + lane) * 8);
+          const u32x4 wv = *reinterpret_cast<const u32x4 *>(p.wvfold + ((size_t)(wave * 16 + ks) * 64 + lane) * 8);
           const float f[8] = {yv[ks][0].x, yv[ks][0].y, yv[ks][0].z, yv[ks][0].w, yv[ks][1].x, yv[ks][1].y, yv[ks][1].z, yv[ks][1].w};
-          union { tk_bf16x8 v; u16 h[8]; } xh, xl;
+          union { bf16x8 v; u16 h[8]; } xh, xl;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            xh.h[e] = tk_bf16(f[e]);
-            xl.h[e] = tk_bf16(f[e] - tk_f32(xh.h[e]));
+            xh.h[e] = bf16_bits(f[e]);
+            xl.h[e] = bf16_bits(f[e] - bf16_value(xh.h[e]));
           }
-          acc[hh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tk_bf16x8, wv), xl.v, acc[hh], 0, 0, 0);
-          acc[hh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tk_bf16x8, wv), xh.v, acc[hh], 0, 0, 0);
+          acc[hh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wv), xl.v, acc[hh], 0, 0, 0);
+          acc[hh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wv), xh.v, acc[hh], 0, 0, 0);
         }
       }
 #pragma unroll
@@ -481,11 +470,11 @@ __global__ __launch_bounds__(256) void samtok_post_kernel(SamtokPost p) {
     }
     tk_to_image<1>(a, lds, X0, 32 * wave, fr, fh);
   }
-  tk_f32x16 q1[2], pv[2];
+  f32x16 q1[2], pv[2];
   tk_load_rows<2>(q1, p.q1, TK_C, row, valid, c0, fh);
   tk_load_rows<2>(pv, p.pe, TK_C, row, valid, c0, fh);
   __syncthreads();
-  tk_f32x16 q2[2];
+  f32x16 q2[2];
   tk_zero<2>(q2);
   tk_gemm<2>(q2, p.o2.w, 8, 2 * wave, 0, 4, lds, X0, lane);          // K = 128
   tk_bias<2>(q2, p.o2.b, c0, fh, false);
@@ -497,11 +486,11 @@ __global__ __launch_bounds__(256) void samtok_post_kernel(SamtokPost p) {
   tk_to_image<2>(q2, lds, X1, c0, fr, fh);
   __syncthreads();
   // MLP: eight 256-column slices of the hidden layer
-  tk_f32x16 y[2];
+  f32x16 y[2];
   tk_zero<2>(y);
 #pragma unroll 1
   for (int c = 0; c < 8; ++c) {
-    tk_f32x16 e[2];
+    f32x16 e[2];
     tk_zero<2>(e);
     tk_gemm<2>(e, p.l1.w, 16, 8 * c + 2 * wave, 0, 8, lds, X1, lane);
     tk_bias<2>(e, p.l1.b, 256 * c + c0, fh, true);
@@ -519,7 +508,7 @@ __global__ __launch_bounds__(256) void samtok_post_kernel(SamtokPost p) {
   tk_store_rows<2>(y, p.q3_out, TK_C, row, valid, c0, fh);
   // k_proj(q3 + pe), v_proj(q3) of the image->token attention
   {
-    tk_f32x16 x[2];
+    f32x16 x[2];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
@@ -528,7 +517,7 @@ __global__ __launch_bounds__(256) void samtok_post_kernel(SamtokPost p) {
     tk_to_image<2>(y, lds, X1, c0, fr, fh);
   }
   __syncthreads();
-  tk_f32x16 kt[1], vt[1];
+  f32x16 kt[1], vt[1];
   tk_zero<1>(kt);
   tk_gemm<1>(kt, p.k3.w, 16, wave, 0, 8, lds, X0, lane);
   tk_bias<1>(kt, p.k3.b, 32 * wave, fh, false);
@@ -549,8 +538,8 @@ __global__ __launch_bounds__(256) void samtok_post_kernel(SamtokPost p) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int h = 2 * wave + (q >> 1), col = 32 * wave + 4 * fh + 8 * q;
-      const unsigned lo = (unsigned)tk_bf16(kt[0][4 * q]) | ((unsigned)tk_bf16(kt[0][4 * q + 1]) << 16);
-      const unsigned hi = (unsigned)tk_bf16(kt[0][4 * q + 2]) | ((unsigned)tk_bf16(kt[0][4 * q + 3]) << 16);
+      const unsigned lo = (unsigned)bf16_bits(kt[0][4 * q]) | ((unsigned)bf16_bits(kt[0][4 * q + 1]) << 16);
+      const unsigned hi = (unsigned)bf16_bits(kt[0][4 * q + 2]) | ((unsigned)bf16_bits(kt[0][4 * q + 3]) << 16);
       *reinterpret_cast<uint2 *>(p.kexp_out + ((size_t)prompt * 64 + h * 8 + tok) * 128 + col) = make_uint2(lo, hi);
     }
   }
@@ -568,16 +557,16 @@ __global__ __launch_bounds__(256) void samtok_post_kernel(SamtokPost p) {
   }
   __syncthreads();
   if (p.k256_out)
-    tk_head_fold(p.wqfold, lds, X0, wave, lane, [&](int h, int nt, const tk_f32x16 &acc) __attribute__((always_inline)) {
+    tk_head_fold(p.wqfold, lds, X0, wave, lane, [&](int h, int nt, const f32x16 &acc) __attribute__((always_inline)) {
       tk_store_fold(p.k256_out, prompt, tok, pok, tok_ok, h, 64 * wave + 32 * nt, fh, acc, 1.0f);
     });
   if (p.vpt_out)
-    tk_head_fold(p.wofold, lds, X1, wave, lane, [&](int h, int nt, const tk_f32x16 &acc) __attribute__((always_inline)) {
+    tk_head_fold(p.wofold, lds, X1, wave, lane, [&](int h, int nt, const f32x16 &acc) __attribute__((always_inline)) {
       if (!pok) return;
       // vpt[b, n, h*8 + tok]: 2-byte stores; the eight token lanes of a prompt make a 16-byte run
       u16 *dst = p.vpt_out + ((size_t)prompt * 256 + 64 * wave + 32 * nt + 4 * fh) * 64 + h * 8 + tok;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) dst[(size_t)((r & 3) + 8 * (r >> 2)) * 64] = tok_ok ? tk_bf16(acc[r]) : (u16)0;
+      for (int r = 0; r < 16; ++r) dst[(size_t)((r & 3) + 8 * (r >> 2)) * 64] = tok_ok ? bf16_bits(acc[r]) : (u16)0;
     });
 }
 

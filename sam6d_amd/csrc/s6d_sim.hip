@@ -31,7 +31,6 @@
 
 namespace s6d {
 
-typedef __attribute__((ext_vector_type(4))) float sim_f32x4;
 
 constexpr int SIM_THREADS = 512;
 constexpr int SIM_WAVES = SIM_THREADS / 64;
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(SIM_THREADS) void cosine_sim_kernel(const float *__
     __syncthreads();
     if (!has_tile || j0 + ct * 16 >= M2 || r0 + rt * 16 >= M1) continue;   // (wave-uniform) nothing of this tile is stored
     const float *ap = As + (rt * 16 + c) * S + g, *bp = Bs + (ct * 16 + c) * S + g;
-    sim_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int k = 0;
     for (; k + 32 <= C; k += 32) {                                       // eight instructions' operands are read ahead of the first
       float a[8], bv[8];
