@@ -20,14 +20,13 @@
 //   * 8 waves = 2 (M) x 4 (N); a wave owns 128 x 64 of the tile as 4 x 2 MFMA tiles (v_mfma_f32_32x32x16_bf16).  The
 //     product is formed TRANSPOSED (W fragment as the A operand, activation fragment as B): a lane then holds one output
 //     row and 4 consecutive output columns per register quad, which makes the epilogue stores 16 B per lane.
-//   * a K tile is 4 phases (one 64 x 32 quadrant of the wave's tile over the whole K step each); the two wave groups
-//     (M halves) run one barrier apart, so on every SIMD one wave is in its matrix segment (8 MFMAs) while the other issues
-//     its fragment reads and DMA: phase = { ds_read, DMA issue, [counted wait], barrier, 8 x MFMA, barrier }.
+//   * a K tile is 2 phases (one 64 x 64 half of the wave's tile over the whole K step each; see "History" below for the template's
+//     four); the two wave groups (M halves) run one barrier apart, so on every SIMD one wave is in its matrix segment (16 MFMAs) while
+//     the other issues its fragment reads and DMA: phase = { ds_read, DMA issue, [counted wait], barrier, 16 x MFMA, barrier }.
 //   * EPI 2 / 3 / 4 (round 3): the residual add and the LayerNorm of a ViT block folded into the GEMMs on either side of them
 //     (x + proj(..), x + lin2(..); LN1 -> qkv, LN2 -> lin1 + GELU): see "Residual add and LayerNorm around the GEMM" below.
 //   * epilogue in registers: bias is the accumulator's initial value, erf-form GELU as relu(x) - |x| 2^P(|x|) (gelu_erf below:
-//     relative error 6e-6), round to bf16,
-//     v_permlane32_swap pairs the two lane halves into 16-byte row segments.
+//     relative error 6e-6), round to bf16, 4 x 4 transpose inside every lane quad: 64 contiguous bytes of a row per quad and store.
 //   * MI (template parameter of gemm_body / gemm2_bf16_kernel): the bf16 matrix instruction, 32 = 32x32x16 as described here, 16 =
 //     16x16x32 on the same schedule (see gemm_body); selected per launch (s6d_set_gemm_mfma_shape, gemm_launch).
 #include "s6d_gemm_params.h"
@@ -73,29 +72,26 @@ namespace s6d {
 
 // Epilogue layout.  Measured on the ViT-H shapes (profiles/r02_gemm_variants.json): the same kernel without its stores runs
 // qkv / proj 25 % faster -- the stores, not the matrix work, are the largest loss at K = 1280.  In the accumulator layout a lane
-// owns ONE output row, so a 16-byte-per-lane store instruction touches 64 different rows: 64 write requests of 16 B.  With
-// S6D_GEMM_QT (default) the four lanes of a quad exchange their four 16-byte chunks (a 4 x 4 transpose by DPP quad_perm) so
+// owns ONE output row, so a 16-byte-per-lane store instruction touches 64 different rows: 64 write requests of 16 B.  Here
+// the four lanes of a quad exchange their four 16-byte chunks (a 4 x 4 transpose by DPP quad_perm) so
 // that a quad holds 64 contiguous bytes of one row: 16 requests of 64 B per instruction.  Two things make that possible without
 // a second exchange: the W rows are fed to the matrix instruction in a permuted order (lane half hb owns columns 32 hb ..
 // 32 hb + 31 of the wave's 64, tile nt the 16-column group nt of each half), which also removes the permlane32 swaps.
 // Tried and dropped (same file): the epilogue rolled quadrant by quadrant into the next tile's first K tile (-3 %: its VALU work
 // lengthens the load segments) and start-time staggering of the workgroups (-4 %).
-#ifndef S6D_GEMM_QT
-#define S6D_GEMM_QT 1
-#endif
-// Main loop.  S6D_GEMM_PH2 = 1: TWO phases per K tile (16-MFMA segments: half the workgroup barriers per MFMA; a phase's load segment
-// = 16 / 8 fragment reads + 4 LDS-DMA pieces against 512 cycles of the partner's matrix segment) instead of the four 8-MFMA phases of
-// the template (S6D_GEMM_PH2 = 0).  Measured in one process, two interleaved rounds (profiles/r02_gemm_variants_ph2.json): +3..4 % on
-// all four ViT-H shapes (qkv 1161 -> 1202, proj 1115 -> 1140, lin1 + GELU 1025 -> 1047, lin2 1247 -> 1285 TFLOP/s): the default.
-#ifndef S6D_GEMM_PH2
-#define S6D_GEMM_PH2 1
-#endif
-#ifndef S6D_GEMM_AUX_A
-#define S6D_GEMM_AUX_A 0
-#endif
-#ifndef S6D_GEMM_AUX_B
-#define S6D_GEMM_AUX_B 0
-#endif
+//
+// History -- three compile-time alternatives that were tried, measured and then removed from this file.  Commit e85ff96 is the last one
+// that holds their code: check it out to measure again (the fp8, MX-output and 16x16x32 kernels, written later, never built with
+// either of the first two).
+//   * S6D_GEMM_QT = 0, the untransposed epilogue: one 32 x 32 accumulator tile at a time, v_permlane32_swap pairing the lane halves
+//     into 16-byte row segments, W rows fed in natural order -- the 64 requests of 16 B per store instruction described above.
+//   * S6D_GEMM_PH2 = 0, the template's main loop of FOUR 8-MFMA phases per K tile (one 64 x 32 quadrant of the wave's tile each, counted
+//     waits vmcnt(8) / (6)).  The two-phase loop below (16-MFMA segments: half the workgroup barriers per MFMA; a phase's load segment
+//     = 16 / 8 fragment reads + 4 LDS-DMA pieces against 512 cycles of the partner's matrix segment) measured +3..4 % on all four
+//     ViT-H shapes in one process, two interleaved rounds (profiles/r02_gemm_variants_ph2.json: qkv 1161 -> 1202, proj 1115 -> 1140,
+//     lin1 + GELU 1025 -> 1047, lin2 1247 -> 1285 TFLOP/s).
+//   * S6D_GEMM_AUX_A / _B, cache-policy bits of the LDS-DMA of the activation / weight stream (2 = nt, "streaming"): what they
+//     measured is in profiles/r03_lnfold.txt; both streams use policy 0.
 // Also tried and dropped: draining the ring (vmcnt(0)) before the stores so that no counted wait sits behind them for 7 phases --
 // the single vector-memory counter makes a counted wait behind 16 stores wait for their acknowledgement -- measured -8 % (the drain
 // itself exposes a load latency per tile and the store cost did not move: profiles/r02_gemm_variants_qt_drain.json).
@@ -195,36 +191,19 @@ __device__ __forceinline__ unsigned pack_out(float lo, float hi) {
 //     order, rstd, GELU, rounding), quad transpose and 64-bytes-per-quad stores then run unchanged.
 template <int EPI, bool HAS_BIAS, int DT, bool AMX = false, int MI = 32>
 __device__ __forceinline__ void gemm_body(const GemmParams &p) {
-  static_assert(MI == 32 || (MI == 16 && DT == 0 && EPI <= 4 && S6D_GEMM_QT && S6D_GEMM_PH2),
-                "the 16x16x32 shape is wired for bf16 operands, the two-phase loop and the quad-transposed epilogue");
+  static_assert(MI == 32 || (MI == 16 && DT == 0 && EPI <= 4), "the 16x16x32 shape is wired for bf16 operands");
   static_assert(!AMX || DT == 1, "MX block scales belong to the fp8 operands");
-  static_assert(EPI != 5 || (DT == 1 && S6D_GEMM_QT), "the MX output is the fp8 kernel's, on the quad-transposed layout");
+  static_assert(EPI != 5 || DT == 1, "the MX output is the fp8 kernel's");
+  static_assert(DT == 0 || EPI < 2 || EPI == 5, "the residual K tiles and the folded LayerNorm are wired for bf16 operands");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;       // M half / N quarter of the 256 x 256 tile
 
-  // ---- tile schedule.  Workgroup b runs on XCD b % 8 (observed dispatch rule; used for speed only): XCD x takes a
-  // contiguous range of the logical tile order, its workgroups walk that range with stride (workgroups per XCD), and
-  // the logical order goes down GM m-tiles before moving to the next n-tile, so the tiles one XCD works on at a time share
-  // A panels and W panels through its L2.
-  const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-  const int tq = p.ntiles >> 3, tr = p.ntiles & 7;
-  const int first = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-  const int cnt = tq + (xcd < tr ? 1 : 0);
-  if (bi >= cnt) return;
-  const int my_tiles = (cnt - bi + bpx - 1) / bpx;
+  // ---- tile schedule (GemmTileSchedule, csrc/s6d_gemm_params.h)
+  const GemmTileSchedule sch(blockIdx.x, gridDim.x, p);
+  if (sch.bi >= sch.cnt) return;
+  const int my_tiles = sch.my_tiles();
   const int G = my_tiles * p.nk;                 // K tiles this workgroup streams through
-
-  auto tile_mn = [&](int j, int &m0, int &n0) __attribute__((always_inline)) {
-    const int L = first + bi + j * bpx;
-    const int tpg = p.GM * p.NT;
-    const int grp = L / tpg, rem = L - grp * tpg;
-    const int mf = grp * p.GM;
-    const int gs = min(p.GM, p.MT - mf);
-    const int nn = rem / gs;
-    m0 = (mf + rem - nn * gs) * 256;
-    n0 = nn * 256;
-  };
 
   // ---- staging geometry: wave w fills rows [16 w, 16 w + 16) of a half-tile in two 1-KiB pieces (8 rows x 128 B each);
   // lane -> row (lane >> 3), chunk position (lane & 7); the chunk it fetches is position ^ ((row >> 1) & 7)
@@ -235,7 +214,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   int ia_kt = 0, ia_tile = 0, ib_kt = 0, ib_tile = 0;                   // issue cursors (K tile within the output tile, tile)
   auto set_a = [&](int tile) __attribute__((always_inline)) {
     int m0, n0;
-    tile_mn(tile, m0, n0);
+    sch.tile(tile, 256, m0, n0);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -244,23 +223,18 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   };
   auto set_b = [&](int tile) __attribute__((always_inline)) {
     int m0, n0;
-    tile_mn(tile, m0, n0);
+    sch.tile(tile, 256, m0, n0);
     b_off = (unsigned)(n0 + srow) * p.ldw2 + sc0;
   };
-  // S6D_GEMM_AUX_A / _B: cache-policy bits of the LDS-DMA of the activation / weight stream (2 = nt, "streaming"): experiment knobs,
-  // see profiles/r03_lnfold.txt for what they measured
-  auto dma = [&](const u16 *base, unsigned off, int slot, int piece, bool is_b = false) __attribute__((always_inline)) {
+  auto dma = [&](const u16 *base, unsigned off, int slot, int piece) __attribute__((always_inline)) {
     S6D_LDS(char) *dst = (S6D_LDS(char) *)gemm_smem + slot * kSlot + (wave * 2 + piece) * 1024;
     if (S6D_GEMM_ABLATE & 1) return;
-    if (is_b)
-      __builtin_amdgcn_global_load_lds((const S6D_GLOBAL(void) *)((const char *)base + off), dst, 16, 0, S6D_GEMM_AUX_B);
-    else
-      __builtin_amdgcn_global_load_lds((const S6D_GLOBAL(void) *)((const char *)base + off), dst, 16, 0, S6D_GEMM_AUX_A);
+    __builtin_amdgcn_global_load_lds((const S6D_GLOBAL(void) *)((const char *)base + off), dst, 16, 0, 0);
   };
   auto issue_b = [&](int half, int slot) __attribute__((always_inline)) {
     const unsigned o = b_off + (unsigned)ib_kt * 128u + (unsigned)half * 128u * p.ldw2;
-    dma(p.W, o, slot, 0, true);
-    dma(p.W, o + 8u * p.ldw2 + sd1, slot, 1, true);
+    dma(p.W, o, slot, 0);
+    dma(p.W, o + 8u * p.ldw2 + sd1, slot, 1);
     if (half == 1 && ++ib_kt == p.nk) {
       ib_kt = 0;
       if (++ib_tile < my_tiles) set_b(ib_tile);
@@ -295,14 +269,14 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   auto frag = [&](int slot, unsigned rowbytes, int ks) __attribute__((always_inline)) -> bf16x8 {
     return *reinterpret_cast<const bf16x8 *>(gemm_smem + slot * kSlot + rowbytes + foff[ks]);
   };
-  // W fragment of n tile nt.  S6D_GEMM_QT: matrix row a (= A-operand lane, a = 4 h + 8 qd + e with h = (a >> 2) & 1) is fed W row
+  // W fragment of n tile nt: matrix row a (= A-operand lane, a = 4 h + 8 qd + e with h = (a >> 2) & 1) is fed W row
   // 32 h + 16 nt + 4 qd + e of the wave's 64, so that in the accumulators lane half h owns columns 32 h + 16 nt + {0..15}.
   // (rows mod 16 stay distinct inside every ds_read_b128 lane group: the swizzle stays conflict-free)
   unsigned wfo[2][4];
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
     const int a = lane & 31;
-    const int row = S6D_GEMM_QT ? 32 * ((a >> 2) & 1) + 16 * nt + 4 * (a >> 3) + (a & 3) : 32 * nt + a;
+    const int row = 32 * ((a >> 2) & 1) + 16 * nt + 4 * (a >> 3) + (a & 3);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int hb = lane >> 5;
@@ -341,14 +315,14 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
 #define S6D_LQ (MI == 16 ? 16 * (lane >> 5) + (lane & 12) : (lane & 28))
   int ct = 0, ck = 0;                                                    // compute cursor
   int cm0, cn0;
-  tile_mn(0, cm0, cn0);
+  sch.tile(0, 256, cm0, cn0);
 
   auto load_scales = [&](int m0, int n0) __attribute__((always_inline)) {
     if (DT != 1) return;
     const int a = lane & 31;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      const int row = S6D_GEMM_QT ? 32 * ((a >> 2) & 1) + 16 * nt + 4 * (a >> 3) + (a & 3) : 32 * nt + a;
+      const int row = 32 * ((a >> 2) & 1) + 16 * nt + 4 * (a >> 3) + (a & 3);
       wsc[nt] = (int)p.sw[n0 + wc * 64 + row];
     }
     if (AMX) return;                                                     // the activation scales come per K tile (mx_issue)
@@ -362,7 +336,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   unsigned mx_row = 0;                                                   // dword index of (this lane's row of m tile 0, K tile 0) of the cursor's tile
   auto mx_set = [&](int tile) __attribute__((always_inline)) {
     int m0, n0;
-    tile_mn(tile, m0, n0);
+    sch.tile(tile, 256, m0, n0);
     mx_row = (unsigned)(m0 + wr * 128 + (lane & 31)) * (unsigned)p.nk;
   };
   auto mx_issue = [&]() __attribute__((always_inline)) {               // request the cursor's K tile into xnx[], advance the cursor
@@ -481,9 +455,9 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
       for (int qd = 0; qd < 4; ++qd) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          // register 4 qd + e of lane half h: column 32 h + 16 nt + 4 qd + e (QT) / 32 nt + 8 qd + 4 h + e
-          const int c0 = S6D_GEMM_QT ? 16 * nt + 4 * qd + e : 32 * nt + 8 * qd + e;
-          const int c1 = S6D_GEMM_QT ? c0 + 32 : c0 + 4;
+          // register 4 qd + e of lane half h: column 32 h + 16 nt + 4 qd + e
+          const int c0 = 16 * nt + 4 * qd + e;
+          const int c1 = c0 + 32;
           const float b = HAS_BIAS ? (hi ? bs[c1] : bs[c0]) : 0.f;
           if ((EPI == 3 || EPI == 4)) {
             const float sn = hi ? cs[c1] : cs[c0];
@@ -491,7 +465,6 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
             for (int mt = 0; mt < 4; ++mt) acc[mt][nt][4 * qd + e] = fmaf(ln_sig[mt], b, ln_nmu[mt] * sn);
           } else if (EPI == 2) {
             // bias + residual, both exact in fp32: x + (a W^T + b) is then rounded to bf16 once, in the epilogue
-            static_assert(S6D_GEMM_QT || EPI != 2, "residual registers are laid out for the quad-transposed column order");
             const int r = 4 * qd + e;                                   // column 32 h + 16 nt + r: word (r & 7) >> 1 of piece 2 nt + (r >> 3)
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
@@ -507,43 +480,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     }
   };
 
-  auto epilogue_one = [&](int mt, int nt, int m0, int n0) __attribute__((always_inline)) {   // one 32 x 32 accumulator tile
-    const int hb = lane >> 5;
-    const int m = m0 + wr * 128 + mt * 32 + (lane & 31);
-    unsigned pk[4][2];
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      float v[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = acc[mt][nt][4 * qd + e];
-      if (EPI == 1) gelu_erf4(v);
-      pk[qd][0] = pack_out<DT>(v[0], v[1]);
-      pk[qd][1] = pack_out<DT>(v[2], v[3]);
-    }
-    // quad qd holds columns 8 qd + 4 hb + {0..3}: swapping the upper lane half of quad 2j with the lower lane half of
-    // quad 2j + 1 leaves each lane 8 consecutive columns 16 j + 8 hb + {0..7} of its row
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      uint4 o;
-      {
-        auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * j][0], pk[2 * j + 1][0], false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(pk[2 * j][1], pk[2 * j + 1][1], false, false);
-        o.x = s0[0];
-        o.y = s1[0];
-        o.z = s0[1];
-        o.w = s1[1];
-      }
-      if (S6D_GEMM_ABLATE & 4) {
-#ifndef HIPEMU
-        asm volatile("" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));   // keep the epilogue arithmetic alive
-#endif
-      } else if (m < p.M) {
-        u16 *dst = p.C + (size_t)m * p.ldc + (n0 + wc * 64 + nt * 32 + 16 * j + 8 * hb);
-        *reinterpret_cast<uint4 *>(dst) = o;
-      }
-    }
-  };
-  // S6D_GEMM_QT: the 32 x 64 strip of m tile mt.  A lane holds 4 chunks of 8 consecutive columns of its row (chunk 2 nt + k =
+  // The 32 x 64 strip of m tile mt.  A lane holds 4 chunks of 8 consecutive columns of its row (chunk 2 nt + k =
   // columns 32 h + 16 nt + 8 k ..); the 4 x 4 transpose inside each lane quad turns that into chunk (lane & 3) of the four rows
   // of the quad, i.e. a quad writes 64 contiguous bytes per instruction
   char *ep_base = nullptr;                                               // this tile's store base of the lane and the row stride in bytes
@@ -668,7 +605,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     }
   };
   auto epilogue = [&](int m0, int n0, int nm0, int nn0) __attribute__((always_inline)) {   // (nm0, nn0): the next tile (EPI 2)
-    if (S6D_GEMM_QT && EPI != 5) {
+    if (EPI != 5) {
       // store addresses of the tile, once (round 6): element (row, col) lives at C + row ldc + col, or -- column blocks of width
       // cblk stored as separate (M, cblk) matrices -- at C + ((col / cblk) M + row) cblk + col % cblk; either way the rows of one
       // column are a constant stride apart, so a strip's stores are base + (32 mt + y) * stride (was: a division per strip)
@@ -685,13 +622,8 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
-      if (S6D_GEMM_QT) {
-        epilogue_qt(mt, m0, n0);
-        if (EPI == 2) load_resid(mt, nm0, nn0);
-      } else {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) epilogue_one(mt, nt, m0, n0);
-      }
+      epilogue_qt(mt, m0, n0);
+      if (EPI == 2) load_resid(mt, nm0, nn0);
     }
   };
 #define S6D_MFMA(C, A, B)                                                              \
@@ -703,32 +635,15 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
       else C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0);              \
     }                                                                                  \
   } while (0)
-#define S6D_MSEG(QM, QN)                                                               \
-  do {                                                                                 \
-    S6D_SETPRIO(1);                                                                    \
-    S6D_PIN(wf[QN][0]);                                                                \
-    S6D_PIN(wf[QN][1]);                                                                \
-    S6D_PIN(wf[QN][2]);                                                                \
-    S6D_PIN(wf[QN][3]);                                                                \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                 \
-      S6D_MFMA(acc[2 * QM][QN], wf[QN][ks], xf[0][ks]);                                \
-      S6D_MFMA(acc[2 * QM + 1][QN], wf[QN][ks], xf[1][ks]);                            \
-    }                                                                                  \
-    S6D_PIN(acc[2 * QM][QN]);                                                          \
-    S6D_PIN(acc[2 * QM + 1][QN]);                                                      \
-    S6D_SETPRIO(0);                                                                    \
-  } while (0)
-
-  if (S6D_GEMM_PH2) {
-    // =============================== two phases per K tile ===============================
-    // stream order B0 B1 A0 A1 per K tile, element e in slot e % 10; K tile g: s0 = (4 g) % 10.
-    //   phase A(g): reads W rows (both n tiles) of B[wc >> 1](g) and activation rows 0..63 of A[wr](g); issues B0, B1 of K tile g + 2
-    //               into the slots A(g - 1) left one phase ago; 16 MFMAs: m tiles 0, 1 x n tiles 0, 1
-    //   phase B(g): reads activation rows 64..127; issues A0, A1 of K tile g + 2 into the slots B(g) left one phase ago; counted wait
-    //               "K tile g + 1 has landed" (the 4 half-tiles of K tile g + 2 stay in flight); 16 MFMAs: m tiles 2, 3
-    // A slot is restaged one phase after its last fragment read; that is safe because every load segment ends with lgkmcnt(0)
-    // BEFORE its barrier (the reads are retired when the other wave group, one barrier apart, starts issuing into the slot), and
-    // a landed K tile is read one phase (two barriers) after the wait that retired it.
+  // =============================== main loop: two phases per K tile ===============================
+  // stream order B0 B1 A0 A1 per K tile, element e in slot e % 10; K tile g: s0 = (4 g) % 10.
+  //   phase A(g): reads W rows (both n tiles) of B[wc >> 1](g) and activation rows 0..63 of A[wr](g); issues B0, B1 of K tile g + 2
+  //               into the slots A(g - 1) left one phase ago; 16 MFMAs: m tiles 0, 1 x n tiles 0, 1
+  //   phase B(g): reads activation rows 64..127; issues A0, A1 of K tile g + 2 into the slots B(g) left one phase ago; counted wait
+  //               "K tile g + 1 has landed" (the 4 half-tiles of K tile g + 2 stay in flight); 16 MFMAs: m tiles 2, 3
+  // A slot is restaged one phase after its last fragment read; that is safe because every load segment ends with lgkmcnt(0)
+  // BEFORE its barrier (the reads are retired when the other wave group, one barrier apart, starts issuing into the slot), and
+  // a landed K tile is read one phase (two barriers) after the wait that retired it.
 #define S6D_MFMA8(C, A, B, SA, SB, OPB) C = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, C, 0, 0, 0, SA, OPB, SB)
 #define S6D_MSEG2_H(QM, H, OPB)                                                        \
   do {                                                                                 \
@@ -783,130 +698,12 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
 #else
 #define S6D_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #endif
-    set_b(0);
-    set_a(0);
-    if (AMX) {                                                           // scale dwords of K tile 0: older than every DMA piece below
-      mx_set(0);
-      mx_issue();
-    }
-    issue_b(0, 0);
-    issue_b(1, 1);
-    issue_a(0, 2);
-    issue_a(1, 3);
-    if (G > 1) {
-      issue_b(0, 4);
-      issue_b(1, 5);
-      issue_a(0, 6);
-      issue_a(1, 7);
-      S6D_VMCNT(8);                                                      // K tile 0 has landed, K tile 1 in flight
-    } else {
-      S6D_VMCNT(0);
-    }
-    mx_take();
-    if (EPI == 2) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) load_resid(mt, cm0, cn0);
-    }
-    init_acc(cm0, cn0);
-    load_scales(cm0, cn0);
-    S6D_BARRIER();
-    if (wr == 1) S6D_BARRIER();                                          // the M halves run one barrier apart from here on
-    int s0 = 0;
-    for (int g = 0; g < G; ++g) {
-      const int sA = ring(s0 + 2 + wr), sB = s0 + (wc >> 1);
-      const bool more2 = g + 2 < G;
-      // ---- phase A
-      if (AMX && g + 1 < G) mx_issue();                                  // scale dwords of K tile g + 1, in front of this tile's DMA issues
-      if constexpr (MI == 16) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) wf6[nt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sB * kSlot + wfo6[nt][ks]);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) xf6[mt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sA * kSlot + mt * 2048 + foff6[ks]);
-      } else {
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) wf[nt][ks] = wfrag(sB, nt, ks);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) xf[i][ks] = frag(sA, (unsigned)(i * 4096), ks);
-      }
-      if (more2) {
-        issue_b(0, ring(s0 + 8));                                        // B0, B1 of K tile g + 2 -> slots of A0, A1 (g - 1)
-        issue_b(1, ring(s0 + 9));
-      }
-      S6D_LGKM0();
-      S6D_BARRIER();
-      if constexpr (MI == 16) S6D_MSEG6(0);
-      else S6D_MSEG2(0);
-      S6D_BARRIER();
-      // ---- phase B
-      if constexpr (MI == 16) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks)
-            xf6[mt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sA * kSlot + (4 + mt) * 2048 + foff6[ks]);
-      } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) xf[i][ks] = frag(sA, (unsigned)((2 + i) * 4096), ks);
-      }
-      if (more2) {
-        issue_a(0, s0);                                                  // A0, A1 of K tile g + 2 -> slots of B0, B1 (g)
-        issue_a(1, s0 + 1);
-        S6D_VMCNT(8);                                                    // K tile g + 1 has landed (K tile g + 2: 4 half-tiles in flight)
-      } else {
-        S6D_VMCNT(0);
-      }
-      S6D_LGKM0();
-      S6D_BARRIER();
-      if constexpr (MI == 16) S6D_MSEG6(1);
-      else S6D_MSEG2(1);
-      S6D_BARRIER();
-      s0 = ring(s0 + 4);
-      if (AMX && g + 1 < G) mx_take();                                   // K tile g + 1's scale dwords (landed: older than the counted wait above)
-      if (++ck == p.nk) {
-        ck = 0;
-        if (wr == 0) S6D_BARRIER();
-        if (EPI == 2) {
-          // unconditional on purpose (after the last tile it re-reads that tile and initialises accumulators nobody uses): a load
-          // that is consumed on one path only stays "pending" on the other, and the compiler then drains inside the main loop
-          int nm0, nn0;
-          tile_mn(min(ct + 1, my_tiles - 1), nm0, nn0);
-          epilogue(cm0, cn0, nm0, nn0);
-          ++ct;
-          cm0 = nm0;
-          cn0 = nn0;
-          init_acc(cm0, cn0);
-        } else {
-          epilogue(cm0, cn0, 0, 0);
-          if (++ct < my_tiles) {
-            tile_mn(ct, cm0, cn0);
-            init_acc(cm0, cn0);
-            load_scales(cm0, cn0);
-          }
-        }
-        if (wr == 1) S6D_BARRIER();
-      }
-    }
-    if (wr == 0) S6D_BARRIER();
-#undef S6D_MSEG2
-#undef S6D_MSEG6
-    return;
-  }
-  static_assert(DT != 1 || S6D_GEMM_PH2, "the fp8 operands are wired into the two-phase main loop only");
-  static_assert(DT == 0 || EPI < 2 || EPI == 5, "the residual K tiles and the folded LayerNorm are wired for bf16 operands");
-  static_assert(S6D_GEMM_QT || EPI < 2, "the residual / LayerNorm / MX epilogues extend the quad-transposed epilogue");
-  // ---- prologue: half-tiles 0..6 of the stream (K tile 0 whole; B0 B1 A0 of K tile 1)
   set_b(0);
   set_a(0);
+  if (AMX) {                                                           // scale dwords of K tile 0: older than every DMA piece below
+    mx_set(0);
+    mx_issue();
+  }
   issue_b(0, 0);
   issue_b(1, 1);
   issue_a(0, 2);
@@ -915,85 +712,89 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     issue_b(0, 4);
     issue_b(1, 5);
     issue_a(0, 6);
-    S6D_VMCNT(6);
+    issue_a(1, 7);
+    S6D_VMCNT(8);                                                      // K tile 0 has landed, K tile 1 in flight
   } else {
     S6D_VMCNT(0);
   }
+  mx_take();
   if (EPI == 2) {
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) load_resid(mt, cm0, cn0);
   }
   init_acc(cm0, cn0);
+  load_scales(cm0, cn0);
   S6D_BARRIER();
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) wf[0][ks] = wfrag(wc >> 1, 0, ks);        // B(0), n tile 0
-  if (wr == 1) S6D_BARRIER();                             // the M halves run one barrier apart from here on
-
-  int s0 = 0;                                                            // ring slot of B0 of K tile g: (4 g) % 10
+  if (wr == 1) S6D_BARRIER();                                          // the M halves run one barrier apart from here on
+  int s0 = 0;
   for (int g = 0; g < G; ++g) {
-    const int sA = ring(s0 + 2 + wr);                                    // A[wr](g)
-    const int sB = s0 + (wc >> 1);                                       // B[wc >> 1](g)
-    const int sBn = ring(s0 + 4 + (wc >> 1));                            // B[wc >> 1](g + 1)
-    const bool more1 = g + 1 < G, more2 = g + 2 < G;
-
-    // phase 1: activation rows 0..63 of this wave -> quadrant (0,0)
+    const int sA = ring(s0 + 2 + wr), sB = s0 + (wc >> 1);
+    const bool more2 = g + 2 < G;
+    // ---- phase A
+    if (AMX && g + 1 < G) mx_issue();                                  // scale dwords of K tile g + 1, in front of this tile's DMA issues
+    if constexpr (MI == 16) {
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) wf6[nt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sB * kSlot + wfo6[nt][ks]);
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) xf6[mt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sA * kSlot + mt * 2048 + foff6[ks]);
+    } else {
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) wf[nt][ks] = wfrag(sB, nt, ks);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) xf[i][ks] = frag(sA, (unsigned)(i * 4096), ks);
-    if (more1) issue_a(1, ring(s0 + 7));                                 // A1(g + 1)
+    }
+    if (more2) {
+      issue_b(0, ring(s0 + 8));                                        // B0, B1 of K tile g + 2 -> slots of A0, A1 (g - 1)
+      issue_b(1, ring(s0 + 9));
+    }
+    S6D_LGKM0();
     S6D_BARRIER();
-    S6D_MSEG(0, 0);
+    if constexpr (MI == 16) S6D_MSEG6(0);
+    else S6D_MSEG2(0);
     S6D_BARRIER();
-
-    // phase 2: W rows 32..63 of this wave -> quadrant (0,1)
+    // ---- phase B
+    if constexpr (MI == 16) {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) wf[1][ks] = wfrag(sB, 1, ks);
-    if (more2) issue_b(0, ring(s0 + 8));                                 // B0(g + 2)
-    S6D_BARRIER();
-    S6D_MSEG(0, 1);
-    S6D_BARRIER();
-
-    // phase 3: activation rows 64..127 -> quadrant (1,0)
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+          xf6[mt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sA * kSlot + (4 + mt) * 2048 + foff6[ks]);
+    } else {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) xf[i][ks] = frag(sA, (unsigned)((2 + i) * 4096), ks);
+    }
     if (more2) {
-      issue_b(1, ring(s0 + 9));                                          // B1(g + 2)
-      S6D_VMCNT(8);                                                      // B(g + 1) has landed (4 younger half-tiles in flight)
+      issue_a(0, s0);                                                  // A0, A1 of K tile g + 2 -> slots of B0, B1 (g)
+      issue_a(1, s0 + 1);
+      S6D_VMCNT(8);                                                    // K tile g + 1 has landed (K tile g + 2: 4 half-tiles in flight)
     } else {
       S6D_VMCNT(0);
     }
+    S6D_LGKM0();
     S6D_BARRIER();
-    S6D_MSEG(1, 0);
+    if constexpr (MI == 16) S6D_MSEG6(1);
+    else S6D_MSEG2(1);
     S6D_BARRIER();
-
-    // phase 4: next K tile's W rows 0..31 (wf[0] is free after quadrant (1,0)) -> quadrant (1,1)
-    if (more1) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) wf[0][ks] = wfrag(sBn, 0, ks);
-    }
-    if (more2) {
-      issue_a(0, s0);                                                    // A0(g + 2) into the slot B0(g) just left
-      S6D_VMCNT(6);                                                      // A(g + 1) has landed (3 younger half-tiles in flight)
-    } else {
-      S6D_VMCNT(0);
-    }
-    S6D_BARRIER();
-    S6D_MSEG(1, 1);
-    S6D_BARRIER();
-
     s0 = ring(s0 + 4);
-    if (++ck == p.nk) {                                                  // output tile complete
+    if (AMX && g + 1 < G) mx_take();                                   // K tile g + 1's scale dwords (landed: older than the counted wait above)
+    if (++ck == p.nk) {
       ck = 0;
-      // both M halves run the epilogue in the same interval (their VALU work shares the SIMDs either way; running it
-      // one after the other would leave one wave per SIMD): the leading half waits one barrier, the trailing half gives
-      // one back afterwards, which also restores the one-barrier stagger
       if (wr == 0) S6D_BARRIER();
       if (EPI == 2) {
+        // unconditional on purpose (after the last tile it re-reads that tile and initialises accumulators nobody uses): a load
+        // that is consumed on one path only stays "pending" on the other, and the compiler then drains inside the main loop
         int nm0, nn0;
-        tile_mn(min(ct + 1, my_tiles - 1), nm0, nn0);
+        sch.tile(min(ct + 1, my_tiles - 1), 256, nm0, nn0);
         epilogue(cm0, cn0, nm0, nn0);
         ++ct;
         cm0 = nm0;
@@ -1002,15 +803,17 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
       } else {
         epilogue(cm0, cn0, 0, 0);
         if (++ct < my_tiles) {
-          tile_mn(ct, cm0, cn0);
+          sch.tile(ct, 256, cm0, cn0);
           init_acc(cm0, cn0);
+          load_scales(cm0, cn0);
         }
       }
       if (wr == 1) S6D_BARRIER();
     }
   }
-  if (wr == 0) S6D_BARRIER();                             // same barrier count for both halves
-#undef S6D_MSEG
+  if (wr == 0) S6D_BARRIER();                                            // same barrier count for both halves
+#undef S6D_MSEG2
+#undef S6D_MSEG6
 #undef S6D_MFMA
 #undef S6D_LROW
 #undef S6D_LH
@@ -1065,24 +868,11 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;       // M half / N half of the 256 x 128 tile
 
-  // tile schedule: as version 1 (XCD x takes a contiguous range of the logical order, GM m-tiles per n-tile group)
-  const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-  const int tq = p.ntiles >> 3, tr = p.ntiles & 7;
-  const int first = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-  const int cnt = tq + (xcd < tr ? 1 : 0);
-  if (bi >= cnt) return;
-  const int my_tiles = (cnt - bi + bpx - 1) / bpx;
+  // tile schedule: as version 1, 128 columns per tile
+  const GemmTileSchedule sch(blockIdx.x, gridDim.x, p);
+  if (sch.bi >= sch.cnt) return;
+  const int my_tiles = sch.my_tiles();
   const int G = my_tiles * p.nk;
-  auto tile_mn = [&](int j, int &m0, int &n0) __attribute__((always_inline)) {
-    const int L = first + bi + j * bpx;
-    const int tpg = p.GM * p.NT;
-    const int grp = L / tpg, rem = L - grp * tpg;
-    const int mf = grp * p.GM;
-    const int gs = min(p.GM, p.MT - mf);
-    const int nn = rem / gs;
-    m0 = (mf + rem - nn * gs) * 256;
-    n0 = nn * 128;
-  };
 
   // staging: wave w fills rows [32 w, 32 w + 32) of a slot in four 1-KiB pieces (8 rows x 128 B); lane -> row (lane >> 3),
   // chunk position (lane & 7), fetched chunk = position ^ ((row >> 1) & 7)
@@ -1096,7 +886,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
   int is_kt = 0, is_tile = 0;
   auto set_tile = [&](int tile) __attribute__((always_inline)) {
     int m0, n0;
-    tile_mn(tile, m0, n0);
+    sch.tile(tile, 128, m0, n0);
     w_off = (unsigned)(n0 + srow) * p.ldw2;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -1141,7 +931,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
 
   f32x16 acc[4][2];
   int ct = 0, ck = 0, cm0, cn0;
-  tile_mn(0, cm0, cn0);
+  sch.tile(0, 128, cm0, cn0);
   // MI = 16: as gemm_body -- lane group lg owns the 16 columns from c16 of the wave's 64, register r of n tile nt = column 4 r + (nt ^ up)
   const int lg = lane >> 4, up = lane >> 5, c16 = 32 * (lg & 1) + 16 * up;
   // One offset register per operand (this kernel has none to spare): k step 1 is chunk + 4 = the offset with bit 6 flipped; the W row
@@ -1443,7 +1233,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
         ck = 0;
         epilogue6(cm0, cn0);
         if (++ct < my_tiles) {
-          tile_mn(ct, cm0, cn0);
+          sch.tile(ct, 128, cm0, cn0);
           init_acc6(cm0, cn0);
         }
       }
@@ -1482,7 +1272,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
       ck = 0;
       epilogue(cm0, cn0);
       if (++ct < my_tiles) {
-        tile_mn(ct, cm0, cn0);
+        sch.tile(ct, 128, cm0, cn0);
         init_acc(cm0, cn0);
       }
     }
@@ -1517,7 +1307,7 @@ static int gemm_launch(const void *A, long lda, const void *W, long ldw, const f
 extern "C" int s6d_gemm_f16(const void *A, long lda, const void *W, long ldw, const float *bias, void *C, long ldc, int M, int N, int K,
                             int epilogue, int max_blocks, void *stream) {
   if (epilogue != 0 && epilogue != 1) return S6D_EINVAL;
-  if (N % 256 != 0 || !S6D_GEMM_QT) return S6D_EUNSUPPORTED;            // the 256 x 256-tile kernel only
+  if (N % 256 != 0) return S6D_EUNSUPPORTED;            // the 256 x 256-tile kernel only
   return gemm_launch(A, lda, W, ldw, bias, GemmExtra(), C, ldc, M, N, K, epilogue, 0, max_blocks, stream, 2);
 }
 
@@ -1525,7 +1315,7 @@ extern "C" int s6d_gemm_fp8(const void *A, long lda, const unsigned char *a_scal
                             const float *bias, void *C, long ldc, int M, int N, int K, int epilogue, int max_blocks, void *stream) {
   if (!a_scale || !w_scale) return S6D_EINVAL;
   if (epilogue != 0 && epilogue != 1) return S6D_EINVAL;
-  if (N % 256 != 0 || K % 128 != 0 || !S6D_GEMM_QT || !S6D_GEMM_PH2) return S6D_EUNSUPPORTED;
+  if (N % 256 != 0 || K % 128 != 0) return S6D_EUNSUPPORTED;
   return gemm_launch(A, lda, W, ldw, bias, GemmExtra(), C, ldc, M, N, K, epilogue, 0, max_blocks, stream, 1, a_scale, w_scale);
 }
 
@@ -1535,7 +1325,7 @@ extern "C" int s6d_gemm_fp8_gelu_mx(const void *A, long lda, const unsigned char
                                     const unsigned char *w_scale, const float *bias, void *C8, long ldc, unsigned char *c_scale,
                                     int M, int N, int K, int max_blocks, void *stream) {
   if (!a_scale || !w_scale || !c_scale) return S6D_EINVAL;
-  if (N % 256 != 0 || K % 128 != 0 || !S6D_GEMM_QT || !S6D_GEMM_PH2) return S6D_EUNSUPPORTED;
+  if (N % 256 != 0 || K % 128 != 0) return S6D_EUNSUPPORTED;
   if (ldc < N || (ldc % 16) != 0) return S6D_EINVAL;
   GemmExtra x;
   x.SC = c_scale;
@@ -1550,7 +1340,7 @@ extern "C" int s6d_gemm_fp8_mxa(const void *A, long lda, const unsigned char *a_
                                 const float *bias, void *C, long ldc, int M, int N, int K, int epilogue, int max_blocks, void *stream) {
   if (!a_mx || !w_scale || ((uintptr_t)a_mx & 3)) return S6D_EINVAL;
   if (epilogue != 0 && epilogue != 1) return S6D_EINVAL;
-  if (N % 256 != 0 || K % 128 != 0 || !S6D_GEMM_QT || !S6D_GEMM_PH2) return S6D_EUNSUPPORTED;
+  if (N % 256 != 0 || K % 128 != 0) return S6D_EUNSUPPORTED;
   GemmExtra x;
   x.sa_mx = reinterpret_cast<const unsigned *>(a_mx);
   return gemm_launch(A, lda, W, ldw, bias, x, C, ldc, M, N, K, epilogue, 0, max_blocks, stream, 1, nullptr, w_scale);
@@ -1559,7 +1349,7 @@ extern "C" int s6d_gemm_fp8_mxa(const void *A, long lda, const unsigned char *a_
 extern "C" int s6d_gemm_bf16_res(const void *A, long lda, const void *W, long ldw, const float *bias, const void *R, long ldr,
                                  float *stats_partial, void *C, long ldc, int M, int N, int K, int max_blocks, void *stream) {
   if (!R || ldr < N || (ldr % 8) || ((uintptr_t)R & 15)) return S6D_EINVAL;
-  if (N % 256 != 0 || !S6D_GEMM_QT) return S6D_EUNSUPPORTED;            // the quad-transposed epilogue of the 256 x 256 kernel
+  if (N % 256 != 0) return S6D_EUNSUPPORTED;            // the quad-transposed epilogue of the 256 x 256 kernel
   GemmExtra x;
   x.R = R;
   x.ldr = ldr;
@@ -1572,7 +1362,7 @@ extern "C" int s6d_gemm_bf16_lnfold(const void *A, long lda, const float *row_st
                                     int max_blocks, void *stream) {
   if (!row_stats || !col_sums || !bias) return S6D_EINVAL;
   if (gelu != 0 && gelu != 1) return S6D_EINVAL;
-  if (N % 256 != 0 || !S6D_GEMM_QT) return S6D_EUNSUPPORTED;
+  if (N % 256 != 0) return S6D_EUNSUPPORTED;
   GemmExtra x;
   x.RS = row_stats;
   x.CS = col_sums;
@@ -1598,7 +1388,7 @@ static int gemm_launch(const void *A, long lda, const void *W, long ldw, const f
   if (M == 0) return S6D_OK;                                            // an empty row batch: nothing to launch
   if (!A || !W || !C) return S6D_EINVAL;
   if (col_block < 0 || (col_block % 8) != 0 || (col_block > 0 && N % col_block != 0)) return S6D_EINVAL;
-  if (col_block > 0 && (N % 256 != 0 || !S6D_GEMM_QT)) return S6D_EUNSUPPORTED;   // the quad-transposed epilogue of the 256 x 256 kernel
+  if (col_block > 0 && N % 256 != 0) return S6D_EUNSUPPORTED;   // the quad-transposed epilogue of the 256 x 256 kernel
   if (N % 128 != 0 || K % kstep != 0 || lda < K || ldw < K || ldc < N) return S6D_EINVAL;
   if ((lda % ralign) || (ldw % ralign) || (ldc % 8)) return S6D_EINVAL;  // 16-byte rows
   if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) return S6D_EINVAL;
@@ -1651,111 +1441,36 @@ static int gemm_launch(const void *A, long lda, const void *W, long ldw, const f
   if (impl == 1 && g_s6d_gemm_wave_tile != 64 && mi == 32 && !x.sa_mx && gemm4_supports(p, epilogue, dt) &&
       (g_s6d_gemm_wave_tile == 128 || gemm4_default(p, epilogue, dt)))
     return gemm4_launch(p, epilogue, max_blocks, st, dt);
-  if (impl == 2) {
-    if (max_blocks <= 0) max_blocks = 512;                               // two persistent workgroups per CU
-    int grid = p.ntiles < max_blocks ? p.ntiles : max_blocks;
-    grid = (grid + 7) & ~7;
-    const size_t lds = (size_t)5 * kSlot;
-#define S6D_GEMM2_LAUNCH_MI(E, HB, D, I)                                                                                \
-  do {                                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm2_bf16_kernel<E, HB, D, I>),                          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-    hipLaunchKernelGGL((gemm2_bf16_kernel<E, HB, D, I>), dim3(grid), dim3(256), lds, st, p);                            \
-  } while (0)
-#define S6D_GEMM2_LAUNCH(E, HB, D)                                                                                      \
-  do {                                                                                                                  \
-    if (D == 0 && mi == 16) S6D_GEMM2_LAUNCH_MI(E, HB, 0, 16); else S6D_GEMM2_LAUNCH_MI(E, HB, D, 32);                  \
-  } while (0)
-    if (dt == 2) {
-      if (epilogue == 1) {
-        if (bias) S6D_GEMM2_LAUNCH(1, true, 2); else S6D_GEMM2_LAUNCH(1, false, 2);
-      } else {
-        if (bias) S6D_GEMM2_LAUNCH(0, true, 2); else S6D_GEMM2_LAUNCH(0, false, 2);
-      }
-    } else if (epilogue == 2) {
-      if (bias) S6D_GEMM2_LAUNCH(2, true, 0); else S6D_GEMM2_LAUNCH(2, false, 0);
-    } else if (epilogue == 1) {
-      if (bias) S6D_GEMM2_LAUNCH(1, true, 0); else S6D_GEMM2_LAUNCH(1, false, 0);
-    } else {
-      if (bias) S6D_GEMM2_LAUNCH(0, true, 0); else S6D_GEMM2_LAUNCH(0, false, 0);
-    }
-#undef S6D_GEMM2_LAUNCH
-#undef S6D_GEMM2_LAUNCH_MI
-    return launch_status();
+  // Kernel tables: exactly the instantiations the library has.  Rows stand in the order the launcher has always named them -- GELU
+  // before plain, with bias (nb = 0) before without, 16x16x32 (m32 = 0) before 32x32x16 -- which is the order of the kernels in the
+  // code object (the host code's first mention of a kernel decides it: profiles/gemm_dead_variants_isa.md).
+  const int plain = epilogue == 1 ? 0 : 1, nb = bias ? 0 : 1, m32 = mi == 16 ? 0 : 1;
+  if (impl == 2) {                                                       // 256 x 128 tiles, two persistent workgroups per CU
+    static constexpr GemmKernel kMixed[2][2][2] = {                      // [plain][no bias][half]: bf16 at 16x16x32 | IEEE half
+        {{gemm2_bf16_kernel<1, true, 0, 16>, gemm2_bf16_kernel<1, true, 2, 32>}, {gemm2_bf16_kernel<1, false, 0, 16>, gemm2_bf16_kernel<1, false, 2, 32>}},
+        {{gemm2_bf16_kernel<0, true, 0, 16>, gemm2_bf16_kernel<0, true, 2, 32>}, {gemm2_bf16_kernel<0, false, 0, 16>, gemm2_bf16_kernel<0, false, 2, 32>}}};
+    static constexpr GemmKernel kRes[2][2] = {                           // bf16 + residual: [no bias][32x32x16]
+        {gemm2_bf16_kernel<2, true, 0, 16>, gemm2_bf16_kernel<2, true, 0, 32>}, {gemm2_bf16_kernel<2, false, 0, 16>, gemm2_bf16_kernel<2, false, 0, 32>}};
+    static constexpr GemmKernel kBf16At32[2][2] = {                      // bf16 at 32x32x16: [plain][no bias]
+        {gemm2_bf16_kernel<1, true, 0, 32>, gemm2_bf16_kernel<1, false, 0, 32>}, {gemm2_bf16_kernel<0, true, 0, 32>, gemm2_bf16_kernel<0, false, 0, 32>}};
+    const GemmKernel k = dt == 2 ? kMixed[plain][nb][1] : epilogue == 2 ? kRes[nb][m32] : mi == 16 ? kMixed[plain][nb][0] : kBf16At32[plain][nb];
+    return gemm_launch_kernel(k, 256, gemm_grid(p.ntiles, max_blocks, 512), (size_t)5 * kSlot, st, p);
   }
-  if (max_blocks <= 0) max_blocks = 256;                                 // one persistent workgroup per CU
-  int grid = p.ntiles < max_blocks ? p.ntiles : max_blocks;
-  grid = (grid + 7) & ~7;                                                // whole XCD rounds
-  const size_t lds = (size_t)kRing * kSlot;
-#define S6D_GEMM_LAUNCH_MI(E, HB, I)                                                                                    \
-  do {                                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_bf16_kernel<E, HB, I>),                              \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-    hipLaunchKernelGGL((gemm_bf16_kernel<E, HB, I>), dim3(grid), dim3(512), lds, st, p);                                \
-  } while (0)
-#define S6D_GEMM_LAUNCH(E, HB)                                                                                          \
-  do {                                                                                                                  \
-    if (mi == 16) S6D_GEMM_LAUNCH_MI(E, HB, 16); else S6D_GEMM_LAUNCH_MI(E, HB, 32);                                    \
-  } while (0)
-#define S6D_GEMM8_LAUNCH(E, HB)                                                                                         \
-  do {                                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_fp8_kernel<E, HB>),                                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-    hipLaunchKernelGGL((gemm_fp8_kernel<E, HB>), dim3(grid), dim3(512), lds, st, p);                                    \
-  } while (0)
-#define S6D_GEMM8X_LAUNCH(E, HB)                                                                                        \
-  do {                                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_fp8mx_kernel<E, HB>),                                \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-    hipLaunchKernelGGL((gemm_fp8mx_kernel<E, HB>), dim3(grid), dim3(512), lds, st, p);                                  \
-  } while (0)
-  if (dt == 1 && x.sa_mx) {
-    if (epilogue == 1) {
-      if (bias) S6D_GEMM8X_LAUNCH(1, true); else S6D_GEMM8X_LAUNCH(1, false);
-    } else {
-      if (bias) S6D_GEMM8X_LAUNCH(0, true); else S6D_GEMM8X_LAUNCH(0, false);
-    }
-    return launch_status();
-  }
-#undef S6D_GEMM8X_LAUNCH
-  if (dt == 1) {
-    if (epilogue == 5) {
-      if (bias) S6D_GEMM8_LAUNCH(5, true); else S6D_GEMM8_LAUNCH(5, false);
-    } else if (epilogue == 1) {
-      if (bias) S6D_GEMM8_LAUNCH(1, true); else S6D_GEMM8_LAUNCH(1, false);
-    } else {
-      if (bias) S6D_GEMM8_LAUNCH(0, true); else S6D_GEMM8_LAUNCH(0, false);
-    }
-    return launch_status();
-  }
-#define S6D_GEMMH_LAUNCH(E, HB)                                                                                         \
-  do {                                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_f16_kernel<E, HB>),                                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-    hipLaunchKernelGGL((gemm_f16_kernel<E, HB>), dim3(grid), dim3(512), lds, st, p);                                    \
-  } while (0)
-  if (dt == 2) {
-    if (epilogue == 1) {
-      if (bias) S6D_GEMMH_LAUNCH(1, true); else S6D_GEMMH_LAUNCH(1, false);
-    } else {
-      if (bias) S6D_GEMMH_LAUNCH(0, true); else S6D_GEMMH_LAUNCH(0, false);
-    }
-    return launch_status();
-  }
-#undef S6D_GEMMH_LAUNCH
-#undef S6D_GEMM8_LAUNCH
-  if (epilogue == 4) {
-    S6D_GEMM_LAUNCH(4, true);
-  } else if (epilogue == 3) {
-    S6D_GEMM_LAUNCH(3, true);
-  } else if (epilogue == 2) {
-    if (bias) S6D_GEMM_LAUNCH(2, true); else S6D_GEMM_LAUNCH(2, false);
-  } else if (epilogue == 1) {
-    if (bias) S6D_GEMM_LAUNCH(1, true); else S6D_GEMM_LAUNCH(1, false);
-  } else {
-    if (bias) S6D_GEMM_LAUNCH(0, true); else S6D_GEMM_LAUNCH(0, false);
-  }
-#undef S6D_GEMM_LAUNCH
-#undef S6D_GEMM_LAUNCH_MI
-  return launch_status();
+  // 256 x 256 tiles, one persistent workgroup of eight waves per CU
+  static constexpr GemmKernel kFp8Mx[2][2] = {                           // [plain][no bias]
+      {gemm_fp8mx_kernel<1, true>, gemm_fp8mx_kernel<1, false>}, {gemm_fp8mx_kernel<0, true>, gemm_fp8mx_kernel<0, false>}};
+  static constexpr GemmKernel kFp8[3][2] = {                             // [MX output | GELU | plain][no bias]
+      {gemm_fp8_kernel<5, true>, gemm_fp8_kernel<5, false>}, {gemm_fp8_kernel<1, true>, gemm_fp8_kernel<1, false>}, {gemm_fp8_kernel<0, true>, gemm_fp8_kernel<0, false>}};
+  static constexpr GemmKernel kF16[2][2] = {                             // [plain][no bias]
+      {gemm_f16_kernel<1, true>, gemm_f16_kernel<1, false>}, {gemm_f16_kernel<0, true>, gemm_f16_kernel<0, false>}};
+  static constexpr GemmKernel kBf16[5][2][2] = {                         // [4 - epilogue][no bias][32x32x16]; the folded LayerNorm (4, 3) always has a bias
+      {{gemm_bf16_kernel<4, true, 16>, gemm_bf16_kernel<4, true, 32>}, {gemm_bf16_kernel<4, true, 16>, gemm_bf16_kernel<4, true, 32>}},
+      {{gemm_bf16_kernel<3, true, 16>, gemm_bf16_kernel<3, true, 32>}, {gemm_bf16_kernel<3, true, 16>, gemm_bf16_kernel<3, true, 32>}},
+      {{gemm_bf16_kernel<2, true, 16>, gemm_bf16_kernel<2, true, 32>}, {gemm_bf16_kernel<2, false, 16>, gemm_bf16_kernel<2, false, 32>}},
+      {{gemm_bf16_kernel<1, true, 16>, gemm_bf16_kernel<1, true, 32>}, {gemm_bf16_kernel<1, false, 16>, gemm_bf16_kernel<1, false, 32>}},
+      {{gemm_bf16_kernel<0, true, 16>, gemm_bf16_kernel<0, true, 32>}, {gemm_bf16_kernel<0, false, 16>, gemm_bf16_kernel<0, false, 32>}}};
+  const GemmKernel k = dt == 1 ? (x.sa_mx ? kFp8Mx[plain][nb] : kFp8[epilogue == 5 ? 0 : 1 + plain][nb])
+                     : dt == 2 ? kF16[plain][nb]
+                               : kBf16[4 - epilogue][nb][m32];
+  return gemm_launch_kernel(k, 512, gemm_grid(p.ntiles, max_blocks, 256), (size_t)kRing * kSlot, st, p);
 }

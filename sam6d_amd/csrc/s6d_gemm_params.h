@@ -32,6 +32,37 @@ struct GemmParams {
                       // (the qkv projection writes q / k / v head-major for the attention kernels: every head's rows contiguous)
 };
 
+// Tile schedule of the persistent kernels.  Workgroup b runs on XCD b % 8 (observed dispatch rule; used for speed only): XCD x takes a
+// contiguous range of the logical tile order, its workgroups walk that range with stride bpx (workgroups per XCD), and the logical
+// order goes down GM m-tiles before moving to the next n-tile, so the tiles one XCD works on at a time share A panels and W panels
+// through its L2.  A workgroup with bi >= cnt has no tile and returns; the others run my_tiles() tiles.
+// (block and grid are unsigned, as blockIdx.x and gridDim.x are, and my_tiles() is not a member filled by the constructor: a signed
+// shift, or the division in front of the early return, changes the code of every kernel -- profiles/gemm_dead_variants_isa.md.)
+struct GemmTileSchedule {
+  const GemmParams &p;
+  int first, bi, bpx, cnt;   // first tile of the XCD's range, this workgroup's index on its XCD, workgroups per XCD, tiles of the XCD
+  __device__ __forceinline__ GemmTileSchedule(unsigned block, unsigned grid, const GemmParams &p_) : p(p_) {
+    const int xcd = block & 7;
+    bi = block >> 3;
+    bpx = grid >> 3;
+    const int tq = p.ntiles >> 3, tr = p.ntiles & 7;
+    first = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
+    cnt = tq + (xcd < tr ? 1 : 0);
+  }
+  __device__ __forceinline__ int my_tiles() const { return (cnt - bi + bpx - 1) / bpx; }
+  // first row and column of this workgroup's j-th tile (256 rows x tile_cols columns)
+  __device__ __forceinline__ void tile(int j, int tile_cols, int &m0, int &n0) const {
+    const int L = first + bi + j * bpx;
+    const int tpg = p.GM * p.NT;
+    const int grp = L / tpg, rem = L - grp * tpg;
+    const int mf = grp * p.GM;
+    const int gs = min(p.GM, p.MT - mf);
+    const int nn = rem / gs;
+    m0 = (mf + rem - nn * gs) * 256;
+    n0 = nn * tile_cols;
+  }
+};
+
 // One stage of the 4 x 4 dword transpose inside every lane quad (the quad-transposed epilogue of both kernel forms), for four
 // register pairs at once: lane bit BIT (0: partner = lane ^ 1, quad_perm [1,0,3,2]; 1: partner = lane ^ 2, quad_perm [2,3,0,1])
 // decides which element of a pair (a, b) a lane keeps -- lanes with the bit clear keep a and take the partner's a into b, lanes with
@@ -77,6 +108,21 @@ __device__ __forceinline__ void quad_xchg4(unsigned (&a)[4], unsigned (&b)[4]) {
   }
 }
 #endif
+
+// ---- host side, shared by gemm_launch (csrc/s6d_gemm.hip) and gemm4_launch (csrc/s6d_gemm4.hip)
+// Persistent grid: one workgroup per output tile up to max_blocks (<= 0: `resident`, the workgroups the kernel form keeps on the 256
+// CUs: 256, or 512 for the two-per-CU 256 x 128 form), in whole XCD rounds of 8 (surplus workgroups return at once).
+inline int gemm_grid(int ntiles, int max_blocks, int resident) {
+  if (max_blocks <= 0) max_blocks = resident;
+  return ((ntiles < max_blocks ? ntiles : max_blocks) + 7) & ~7;
+}
+// One launch with `lds` bytes of dynamic LDS (above 64 KiB a kernel needs the attribute first; it is set on every launch).
+typedef void (*GemmKernel)(GemmParams);
+inline int gemm_launch_kernel(GemmKernel kernel, int block, int grid, size_t lds, hipStream_t st, const GemmParams &p) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, p);
+  return launch_status();
+}
 
 // csrc/s6d_gemm4.hip: the four-wave kernel (bf16 operands, EPI 0 - 4).  Returns S6D_EUNSUPPORTED for what it does not cover.
 int gemm4_launch(const GemmParams &p, int epilogue, int max_blocks, hipStream_t st, int dt);

@@ -12,7 +12,8 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(REPO, "sam6d_amd", "csrc")
 EMU = os.path.join(HERE, "host_cc", "hipemu")
 OUT = os.path.join(HERE, "host_cc", "_build")
-# HIPEMU_EXTRA: extra compiler flags (e.g. "-DS6D_GEMM_ROLL=1" for a kernel variant); each setting gets its own library file
+# HIPEMU_EXTRA: extra compiler flags (e.g. "-DS6D_RPE_FOUR_KEYS_MAX_ROWS=0" for a kernel variant, as tests/test_emu_pose.py passes);
+# each setting gets its own library file
 EXTRA = os.environ.get("HIPEMU_EXTRA", "").split()
 SO = os.path.join(OUT, "libsam6d_emu" + ("_" + re.sub(r"[^A-Za-z0-9]+", "_", "".join(EXTRA)) if EXTRA else "") + ".so")
 CXX = os.environ.get("HIPEMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")

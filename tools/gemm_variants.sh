@@ -1,5 +1,8 @@
 #!/bin/bash
-# Stand-alone builds of the GEMM kernel with profiling switches (csrc/s6d_gemm.hip header) for tools/gemm_time.py:
+# Stand-alone builds of the GEMM kernel with its profiling switches for tools/gemm_time.py.  csrc/s6d_gemm.hip has two:
+#   -DS6D_GEMM_ABLATE=<bits>   1 = no LDS-DMA, 2 = no MFMA (fragment reads stay), 4 = no epilogue stores (built below)
+#   -DS6D_GEMM_NOPRIO          no s_setprio around the matrix segments
+# Output:
 #   tools/gemm_variants/libgemm_<name>.so   (git-ignored; travels with the gpurun snapshot)
 set -e
 cd "$(dirname "$0")/.."
