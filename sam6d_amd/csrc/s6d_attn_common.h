@@ -115,13 +115,6 @@ constexpr int kAbl = S6D_ATTN_ABLATE;
 constexpr float kLog2e = 1.4426950408889634f;
 // v_exp_f32 without the denormal-range fix-up of fast_exp2(): arguments here are <= 2^kDefer and tiny results may flush
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-// A kernel's dynamic LDS.  On the tests' host emulator (HIPEMU) it is a global array; tests/hipemu.py rewrites the declaration in .hip
-// text only, so headers that hold kernels declare it through this macro.
-#ifdef HIPEMU
-#define S6D_ATTN_DYN_LDS(name) extern __attribute__((aligned(16))) char name[]
-#else
-#define S6D_ATTN_DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) char name[]
-#endif
 
 template <int HD>
 struct Cfg {
@@ -577,34 +570,10 @@ struct WinItem {
   }
 };
 
-// ---- LDS-DMA and counted waits (the persistent window kernel and the global64 kernel) ------------------------------------------
+// ---- LDS-DMA (the persistent window kernel and the global64 kernel) --------------------------------------------------------------
+// Both issue their pieces with lds_dma16_m0 and wait with S6D_VMCNT / S6D_LGKM0 (csrc/s6d_mem.h; the functions there are namespace
+// s6d's in both element-type builds, found through the using-directive above).
 __device__ const uint4 g_attn_zero16 = {0u, 0u, 0u, 0u};          // the 16-byte zero that padded / out-of-window chunks are DMA'd from
-#ifdef HIPEMU
-#define S6D_ATTN_VMCNT0() hipemu::vmcnt_wait(0)
-#define S6D_ATTN_VMCNT(n) hipemu::vmcnt_wait(n)
-#define S6D_ATTN_LGKM0()
-#else
-#define S6D_ATTN_VMCNT0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define S6D_ATTN_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define S6D_ATTN_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#endif
-#define S6D_ATTN_GLOBAL(T) __attribute__((address_space(1))) T
-
-// One 1-KiB DMA piece: lane l's 16 bytes at src -> LDS byte address lds + 16 l (lds wave-uniform).  Issued as inline asm, not through
-// __builtin_amdgcn_global_load_lds: with the builtin in the loop hipcc puts an s_waitcnt vmcnt(0) in front of the first
-// ds_read_b64_tr_b16 of every tile (it cannot tell that the reads touch another ring slot), which drains the two-tile look-ahead;
-// the waits here are the counted ones written out below.  M0 is on the clobber list (the library is built with -Wno-inline-asm: hipcc
-// warns about reserved registers there); nothing else in the kernel uses it.
-#ifdef HIPEMU
-#define S6D_ATTN_DMA16(src, lds_ptr) __builtin_amdgcn_global_load_lds((const S6D_ATTN_GLOBAL(void) *)(src), (lds_ptr), 16, 0, 0)
-#else
-__device__ __forceinline__ void attn_dma16(const void *src, S6D_LDS(char) *dst) {
-  const unsigned a = __builtin_amdgcn_readfirstlane((unsigned)(size_t)dst);
-  // s_nop: one wait state between the SALU write of M0 and the LDS-DMA that reads it (hipcc puts the same nop after its own s_mov m0)
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(a) : "memory", "m0");
-}
-#define S6D_ATTN_DMA16(src, lds_ptr) attn_dma16((src), (lds_ptr))
-#endif
 
 // launch with `lds` bytes of dynamic LDS: above 64 KiB a kernel needs the attribute first
 template <class... P, class... A>

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_global_kernel(AttnParams p) {
   // MODE 1 (the aligned 64 x 64 fast path, th tables at a 65-float row stride: S6D_GLB_THLD) ran here until attn_global64_kernel took
   // that grid (docs/NOTEBOOK_r1_r4.md section 4.2, profiles/r02_attn_variants.txt)
   static_assert(MODE == 0 || MODE == 2, "attn_global_kernel: table bias (0) or no bias (2); the 64 x 64 grid is attn_global64_kernel's");
-  S6D_ATTN_DYN_LDS(smem);
+  S6D_DYN_LDS(smem);
   constexpr int KBYTES = 64 * C::KROW * 2, VBYTES = 64 * C::VROW * 2;
   // ring slot r: K image at r*(KBYTES+VBYTES), V image right behind it
   auto Kbuf = [&](int r) { return reinterpret_cast<u16 *>(smem + r * (KBYTES + VBYTES)); };
@@ -148,10 +148,10 @@ struct G64 {
 template <int PW>
 __device__ __forceinline__ void g64_wait_tiles(int n) {
   switch (PW * n) {
-#define S6D_G64_CASE(k) case k: S6D_ATTN_VMCNT(k); break;
+#define S6D_G64_CASE(k) case k: S6D_VMCNT(k); break;
     S6D_G64_CASE(0) S6D_G64_CASE(3) S6D_G64_CASE(5) S6D_G64_CASE(6) S6D_G64_CASE(9) S6D_G64_CASE(10) S6D_G64_CASE(12)
 #undef S6D_G64_CASE
-    default: S6D_ATTN_VMCNT(15); break;              // 15 or more (PW (SLOTS - 2) <= 15 is asserted)
+    default: S6D_VMCNT(15); break;              // 15 or more (PW (SLOTS - 2) <= 15 is asserted)
   }
 }
 
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_global64_kernel(AttnParams p)
   using C = Cfg<HD>;
   using G = G64<HD, WAVES, SLOTS>;
   constexpr int NS = G::NS, PW = G::PW;
-  S6D_ATTN_DYN_LDS(smem);
+  S6D_DYN_LDS(smem);
   float *tabs = reinterpret_cast<float *>(smem + G::RING);
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int g = lane >> 4, c = lane & 15;
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_global64_kernel(AttnParams p)
 #pragma unroll
     for (int i = 0; i < PW; ++i) {
       S6D_LDS(char) *dst = (S6D_LDS(char) *)smem + slot * G::SLOT + dsto[i];
-      S6D_ATTN_DMA16(src[i], dst);
+      lds_dma16_m0(src[i], dst);
       src[i] += inc[i];
     }
   };
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_global64_kernel(AttnParams p)
   auto tile_head = [&](int t, float (&thv)[NS]) __attribute__((always_inline)) -> const u16 * {
     S6D_TICK(tk, 0);
     g64_wait_tiles<PW>(min(D - 1, ntile - 1 - t));
-    S6D_ATTN_LGKM0();
+    S6D_LGKM0();
     __builtin_amdgcn_s_barrier();
     S6D_TICK(tk, 1);
     if (t + D < ntile && !(kAbl & 1)) issue(slot >= 1 ? slot - 1 : SLOTS - 1);

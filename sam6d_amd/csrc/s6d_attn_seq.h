@@ -33,7 +33,7 @@ template <int HD, int WAVES, bool BIAS>
 __global__ __launch_bounds__(WAVES * 64) void attn_window_kernel(AttnParams p) {
   using C = Cfg<HD>;
   constexpr int MODE = BIAS ? 0 : 2;
-  S6D_ATTN_DYN_LDS(smem);
+  S6D_DYN_LDS(smem);
   const int ntile = (p.T + 63) / 64;
   // no bias (sequences): COMPACT images -- K rows up to the last 16-key sub-tile that exists, V rows up to the last 32-key step
   // (win_seq_tile above skips the absent sub-tiles of the tail tile).  257 tokens x head dim 64: 272 x 144 + 288 x 144 = 78.75 KiB instead

@@ -394,7 +394,7 @@ __device__ __forceinline__ void win16_pass_stream(const AttnParams &p, const u16
 template <int HD, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void attn_window16_kernel(AttnParams p) {
   using C = Cfg<HD>;
-  S6D_ATTN_DYN_LDS(smem);
+  S6D_DYN_LDS(smem);
   const int S = p.S, SR = (S + 1) & ~1;                            // key rows, rounded up to a 32-key k-step
   u16 *Kl = reinterpret_cast<u16 *>(smem);                         // [SR*16][KROW]
   u16 *Vl = Kl + (size_t)SR * 16 * C::KROW;                        // [SR*16][VROW]
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(512) void attn_window16p_kernel(AttnParams p, int n
   using C = Cfg<HD>;
   constexpr int WAVES = 8;
   constexpr int KROWT = HD + 8, KCH = KROWT / 8, VCH = C::VROW / 8;   // chunks (16 B) per K / V row
-  S6D_ATTN_DYN_LDS(smem);
+  S6D_DYN_LDS(smem);
   const int S = p.S, SR = (S + 1) & ~1;
   const int kchunks = SR * 16 * KCH, vchunks = SR * 16 * VCH;
   const int kinstr = (kchunks + 63) >> 6, vinstr = (vchunks + 63) >> 6;
@@ -597,9 +597,7 @@ __global__ __launch_bounds__(512) void attn_window16p_kernel(AttnParams p, int n
       const int k = wave + i * WAVES;
       if (k < ninstr) {                                               // wave-uniform
         unsigned cc = which == 1 ? kvc[i] : kvc[i] >> 16;
-#ifndef HIPEMU
-        asm volatile("" : "+v"(cc));        // opaque per item: the unpacked fields must not be hoisted out of the item loop (40 registers)
-#endif
+        S6D_PIN(cc);                        // opaque per item: the unpacked fields must not be hoisted out of the item loop (40 registers)
         const int ky = (int)(cc & 15u), kx = (int)((cc >> 4) & 15u), po = min((int)((cc >> 8) & 15u) * 8, HD - 8);
         const int y = y0 + ky, x = x0 + kx;
         const bool img = (y < p.H) && (x < p.W);
@@ -608,9 +606,7 @@ __global__ __launch_bounds__(512) void attn_window16p_kernel(AttnParams p, int n
         const u16 *src = img ? s_img : bias_base + po;
         const void *sp = (cc >> 12) & 1u ? (const void *)src : (const void *)&g_attn_zero16;
         S6D_LDS(char) *dst = (S6D_LDS(char) *)dst_base + (k << 10);
-        // (inline asm.  The alternative was __builtin_amdgcn_global_load_lds: hipcc then waits vmcnt(0) in front of the next LDS read, so
-        // the prefetch never overlapped the arithmetic: docs/NOTEBOOK_r1_r4.md section 4.2, profiles/r04_win16_dma_waits.txt.)
-        S6D_ATTN_DMA16(sp, dst);
+        lds_dma16_m0(sp, dst);                 // (the inline-asm issue, so that the prefetch overlaps the arithmetic: csrc/s6d_mem.h)
       }
     }
   };
@@ -657,7 +653,7 @@ __global__ __launch_bounds__(512) void attn_window16p_kernel(AttnParams p, int n
   load_q(cur, false, qfa);
   stage_image(cur, 1, smem);
   stage_image(cur, 2, smem + kbytes);
-  S6D_ATTN_VMCNT0();
+  S6D_VMCNT(0);
   __syncthreads();
   int buf = 0;
   long long wtk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wsum[6] = {0, 0, 0, 0, 0, 0};   // S6D_G64_TIMING probe build: phase clocks, see below
@@ -713,7 +709,7 @@ __global__ __launch_bounds__(512) void attn_window16p_kernel(AttnParams p, int n
         win16_pass<HD, 2, 16, false, KROWT, S6D_WIN16_KSWZ != 0>(p, Kl, Vl, S, SR, cur.b, cur.wy, cur.wx, cur.head, wave, WAVES, q2, twr, thv, lane, mid);
     }
     S6D_TICK(wtk, 4);
-    S6D_ATTN_VMCNT0();                                               // next item's images and Q have landed (and this item's stores)
+    S6D_VMCNT(0);                                                  // next item's images and Q have landed (and this item's stores)
     S6D_TICK(wtk, 5);
     __syncthreads();
     S6D_TICK(wtk, 6);

@@ -3,8 +3,7 @@
 // csrc/*.hip is its own translation unit in namespace s6d: a kernel file includes this header and defines none of these itself.
 #pragma once
 #include "s6d_common.h"
-
-#define S6D_LDS(T) __attribute__((address_space(3))) T
+#include "s6d_mem.h"
 
 namespace s6d {
 

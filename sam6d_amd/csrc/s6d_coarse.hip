@@ -21,13 +21,14 @@
 // accumulates in float64 too) in the last bit at most, so a uniform picks a different bin only when it falls within one ulp of a
 // bin boundary; the tests compare the sampled pairs and the final pose.
 #include "s6d_common.h"
+#include "s6d_mem.h"
 
 namespace s6d {
 
 constexpr int CS_THREADS = 1024;
 constexpr int CS_WAVES = CS_THREADS / 64;
 
-extern __shared__ __attribute__((aligned(16))) char cs_smem[];
+S6D_DYN_LDS(cs_smem);
 
 __global__ __launch_bounds__(CS_THREADS) void coarse_sample_kernel(const float *__restrict__ atten, const float *__restrict__ rand_u,
                                                                   int M1, int M2, int n_u, int32_t *__restrict__ pair,

@@ -40,13 +40,6 @@
 
 namespace s6d {
 
-#define FM_GLOBAL(T) __attribute__((address_space(1))) T
-#ifdef HIPEMU
-#define FM_VMCNT0() hipemu::vmcnt_wait(0)
-#else
-#define FM_VMCNT0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#endif
-
 constexpr int FM_C = 256;                  // feature width (fine_point_matching out_dim)
 constexpr int FM_ROWB = FM_C * 4;          // bytes of a split row: hi (C bf16) | lo (C bf16)
 constexpr int FM_TILE = 32;                // stream rows per tile
@@ -57,7 +50,7 @@ constexpr int FM_SIDEB = FM_TILE * FM_SIDE * 4;
 constexpr int FM_NSIDE = 4;                // side-table ring: tile t's table is read one barrier interval after tile t + 2 is staged
 constexpr int FM_LDSB = 2 * FM_TILEB + FM_NSIDE * FM_SIDEB;
 
-extern __shared__ __attribute__((aligned(16))) char fm_smem[];
+S6D_DYN_LDS(fm_smem);
 
 // ---- split: x -> normalise (F.normalize, eps 1e-12) -> * scale -> hi = bf16(x), lo = bf16(x - hi) -------------------------------
 // one wave per row; rows >= M (padding up to a whole tile) are zero
@@ -240,7 +233,7 @@ __global__ void __launch_bounds__(512, 2) fine_sweep_kernel(FineParams p) {
       const int row = wave * 4 + i;
       const char *g = reinterpret_cast<const char *>(sbase + (size_t)(t * FM_TILE + row) * (2 * FM_C)) + ((lane ^ (row & 15)) << 4);
       S6D_LDS(char) *dst = (S6D_LDS(char) *)fm_smem + buf * FM_TILEB + row * FM_ROWB;
-      __builtin_amdgcn_global_load_lds((const FM_GLOBAL(void) *)g, dst, 16, 0, 0);
+      lds_dma16(g, dst);
     }
     if (tid < FM_TILE) {
       float sv[5];
@@ -319,7 +312,7 @@ __global__ void __launch_bounds__(512, 2) fine_sweep_kernel(FineParams p) {
   // matrix work of tile t.  One accumulator set per wave; the MFMA / VALU overlap comes from the two waves of a SIMD being
   // half an iteration apart.
   stage(0, 0);
-  FM_VMCNT0();
+  S6D_VMCNT(0);
   __syncthreads();
   f32x16 acc;
 #pragma unroll
@@ -333,7 +326,7 @@ __global__ void __launch_bounds__(512, 2) fine_sweep_kernel(FineParams p) {
       if (t > 0) epilogue(t - 1, acc);
       tile_mfma(t & 1, acc);
     }
-    FM_VMCNT0();
+    S6D_VMCNT(0);
     __syncthreads();
   }
   if (wave >= 4) epilogue(ntile - 1, acc);

@@ -34,23 +34,7 @@
 
 namespace s6d {
 
-#define S6D_GLOBAL(T) __attribute__((address_space(1))) T
-
-#ifdef HIPEMU
-#define S6D_VMCNT(n) hipemu::vmcnt_wait(n)
-#define S6D_CONST(T) T
-#else
-#define S6D_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define S6D_CONST(T) __attribute__((address_space(4))) T   // uniform address + constant address space = s_load (lgkmcnt, not vmcnt)
-#endif
-// An MFMA is a pure register operation: neither s_barrier nor sched_barrier orders it at instruction-selection time (it has
-// no chain), so the matrix segment is tied down by data: an empty asm makes the operands opaque after the opening barrier
-// (no MFMA can be placed above it) and the accumulators opaque before the closing one (none can sink below it).
-#ifdef HIPEMU
-#define S6D_PIN(x)
-#else
-#define S6D_PIN(x) asm volatile("" : "+v"(x))
-#endif
+// (address spaces, counted waits, the LDS-DMA issue and S6D_PIN, which ties the matrix segments down by data: csrc/s6d_mem.h)
 // hipcc treats s_barrier as a memory fence only: register-only MFMAs drift across it (and past s_setprio) unless pinned
 #define S6D_BARRIER()                     \
   do {                                    \
@@ -118,7 +102,7 @@ namespace s6d {
 constexpr int kSlot = 16384;  // one half-tile: 128 rows x 64 k bf16
 constexpr int kRing = 10;     // slots: all 160 KiB of the CU
 
-extern __shared__ __attribute__((aligned(16))) char gemm_smem[];
+S6D_DYN_LDS(gemm_smem);
 
 __device__ __forceinline__ int ring(int s) { return s >= kRing ? s - kRing : s; }
 __device__ __forceinline__ int ring5(int s) { return s >= 5 ? s - 5 : s; }
@@ -229,7 +213,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
   auto dma = [&](const u16 *base, unsigned off, int slot, int piece) __attribute__((always_inline)) {
     S6D_LDS(char) *dst = (S6D_LDS(char) *)gemm_smem + slot * kSlot + (wave * 2 + piece) * 1024;
     if (S6D_GEMM_ABLATE & 1) return;
-    __builtin_amdgcn_global_load_lds((const S6D_GLOBAL(void) *)((const char *)base + off), dst, 16, 0, 0);
+    lds_dma16((const char *)base + off, dst);
   };
   auto issue_b = [&](int half, int slot) __attribute__((always_inline)) {
     const unsigned o = b_off + (unsigned)ib_kt * 128u + (unsigned)half * 128u * p.ldw2;
@@ -693,11 +677,6 @@ __device__ __forceinline__ void gemm_body(const GemmParams &p) {
     _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) S6D_PIN(acc6[4 * QM + mt][nt]); \
     S6D_SETPRIO(0);                                                                    \
   } while (0)
-#ifdef HIPEMU
-#define S6D_LGKM0()
-#else
-#define S6D_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#endif
   set_b(0);
   set_a(0);
   if (AMX) {                                                           // scale dwords of K tile 0: older than every DMA piece below
@@ -895,7 +874,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
   };
   auto dma = [&](const u16 *base, unsigned off, int slot, int piece) __attribute__((always_inline)) {
     S6D_LDS(char) *dst = (S6D_LDS(char) *)gemm_smem + slot * kSlot + (wave * 4 + piece) * 1024;
-    __builtin_amdgcn_global_load_lds((const S6D_GLOBAL(void) *)((const char *)base + off), dst, 16, 0, 0);
+    lds_dma16((const char *)base + off, dst);
   };
   auto issue_w = [&](int slot) __attribute__((always_inline)) {        // W of the cursor's K tile
     const unsigned k = (unsigned)is_kt * 128u;
@@ -1210,9 +1189,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
       for (int mt = 0; mt < 8; ++mt)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) xf6[mt][ks] = *reinterpret_cast<const bf16x8 *>(gemm_smem + sA * kSlot + mt * 2048 + (xo ^ (unsigned)(64 * ks)));
-#ifndef HIPEMU
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
+      S6D_LGKM0();
       __builtin_amdgcn_s_barrier();
       // four quarter steps (k step, four m tiles); the stream elements go out in front of the first three, as in the 32x32x16 loop
 #pragma unroll
@@ -1248,9 +1225,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmParams p) {
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) xf[mt][ks] = frag(sA, (unsigned)(mt * 32 * 128), ks);
-#ifndef HIPEMU
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // the fragments are in registers ...
-#endif
+    S6D_LGKM0();                                                         // the fragments are in registers ...
     __builtin_amdgcn_s_barrier();                                        // ... everybody's: the three slots of this K tile are free
     // the next three stream elements go out between the matrix instructions of the four k steps
 #pragma unroll

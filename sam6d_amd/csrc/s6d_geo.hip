@@ -157,9 +157,7 @@ struct GeoFromPoints {
     // x * div_term[j] of the sinusoids, with the kernel's default (contraction allowed).  The empty statement keeps the optimiser from
     // looking through x and combining the two sides (during development a prologue without it gave 1-ulp different sinusoid arguments in
     // geo_embed2_kernel; profiles/geo_from_points.md); no instruction, no register.
-#ifndef HIPEMU
-    asm volatile("" : "+v"(x));
-#endif
+    S6D_PIN(x);
     return x;
   }
 };
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed_kernel(const SRC src,
                                                                const float *__restrict__ Wd, const float *__restrict__ bd,
                                                                const float *__restrict__ Wa, const float *__restrict__ ba,
                                                                const float *__restrict__ div_term, void *__restrict__ outv) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  S6D_DYN_LDS(smem);
   u16 *lds = reinterpret_cast<u16 *>(smem);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 15, g = lane >> 4;
@@ -379,13 +377,6 @@ constexpr int G2_WROW = 32;                                        // bf16 per r
 constexpr int G2_PART = GEO_C * G2_WROW;
 constexpr int G2_STAGE = 4 * G2_PART;                              // W_d hi | W_d lo | W_a hi | W_a lo
 constexpr int G2_LDS_BYTES = 2 * G2_STAGE * 2;                     // 128 KB
-#define G2_LDS(T) __attribute__((address_space(3))) T
-#define G2_GLOBAL(T) __attribute__((address_space(1))) T
-#ifdef HIPEMU
-#define G2_VMCNT0() hipemu::vmcnt_wait(0)
-#else
-#define G2_VMCNT0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#endif
 __device__ __forceinline__ int g2_swz(int row) { return ((row >> 3) & 1) << 1; }
 
 template <bool HALF, class SRC>
@@ -393,7 +384,7 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const SRC src, 
                                                                 const float *__restrict__ bd, const u16 *__restrict__ Wa,
                                                                 const float *__restrict__ ba, const float *__restrict__ div_term,
                                                                 void *__restrict__ outv) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  S6D_DYN_LDS(smem);
   u16 *lds = reinterpret_cast<u16 *>(smem);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 15, g = lane >> 4;
@@ -417,8 +408,8 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const SRC src, 
         const int it = tid + n * GEO_THREADS;
         const int row = it >> 2, ch = it & 3;
         const u16 *src = parts[q] + (size_t)row * GEO_C + ks * 32 + ((ch ^ g2_swz(row)) * 8);
-        G2_LDS(char) *dst = (G2_LDS(char) *)smem + ((stage * G2_STAGE + q * G2_PART) * 2 + (wave * 64 + n * GEO_THREADS) * 16);
-        __builtin_amdgcn_global_load_lds((const G2_GLOBAL(void) *)src, dst, 16, 0, 0);
+        S6D_LDS(char) *dst = (S6D_LDS(char) *)smem + ((stage * G2_STAGE + q * G2_PART) * 2 + (wave * 64 + n * GEO_THREADS) * 16);
+        lds_dma16(src, dst);
       }
   };
   // the lane's sinusoid fragments of k-step ks: [embedding] chunk g = frequencies 16 ks + 4 g + j, interleaved [sin, cos] (:279-280)
@@ -454,7 +445,7 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const SRC src, 
   float wq[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) wq[j] = div_term[16 + g * 4 + j];
-  G2_VMCNT0();
+  S6D_VMCNT(0);
   __syncthreads();
 #pragma unroll 1
   for (int ks = 0; ks < GEO_C / 32; ++ks) {
@@ -517,7 +508,7 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_embed2_kernel(const SRC src, 
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) wq[j] = wq2[j];
-    G2_VMCNT0();                                                   // the next slice has landed (issued ~1500 matrix-pipe cycles ago)
+    S6D_VMCNT(0);                                                 // the next slice has landed (issued ~1500 matrix-pipe cycles ago)
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(kPsThreads) void patch_scores_kernel(const float *_
                                                                  float *__restrict__ part_rowsum,
                                                                  float *__restrict__ part_colmax,
                                                                  int *__restrict__ part_nnz) {
-  extern __shared__ __attribute__((aligned(16))) char ps_smem[];
+  S6D_DYN_LDS(ps_smem);
   unsigned short *lds = reinterpret_cast<unsigned short *>(ps_smem);
   const int s = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 15, g = lane >> 4;

@@ -13,16 +13,11 @@
 // 64 rows, so kv[c][d] is wave-uniform and rides as the scalar operand of v_fmac_f32: no LDS, no staging -- and writes the merged
 // (B, I, 256) layout.  fp32 throughout, sequential sums over c and j.
 #include "s6d_common.h"
+#include "s6d_mem.h"
 
 namespace s6d {
 
 constexpr int LA_C = 256, LA_H = 4, LA_D = 64;
-
-#ifdef HIPEMU
-#define S6D_LA_CONST(T) T
-#else
-#define S6D_LA_CONST(T) __attribute__((address_space(4))) T
-#endif
 
 // one workgroup per (batch, head): thread t -> kv[c = t >> 2][16 (t & 3) .. + 15];  keys / values staged through LDS 28 rows at a time
 __global__ __launch_bounds__(256) void linattn_kv_kernel(const float *__restrict__ kf, long ldk, const float *__restrict__ v, long ldv,
@@ -90,8 +85,8 @@ __global__ __launch_bounds__(256) void linattn_apply_kernel(const float *__restr
   n3 = (part[1][0][lane] + part[1][1][lane]) + (part[1][2][lane] + part[1][3][lane]);
   const float f = sqrtf(n1) / sqrtf(n3);
   // (q kv) and q . ksum with kv / ksum of this (batch, head) as scalar operands
-  const S6D_LA_CONST(float) *kvs = (const S6D_LA_CONST(float) *)kv + (size_t)(b * LA_H + h) * LA_D * LA_D;
-  const S6D_LA_CONST(float) *kss = (const S6D_LA_CONST(float) *)ksum + (size_t)(b * LA_H + h) * LA_D;
+  const S6D_CONST(float) *kvs = (const S6D_CONST(float) *)kv + (size_t)(b * LA_H + h) * LA_D * LA_D;
+  const S6D_CONST(float) *kss = (const S6D_CONST(float) *)ksum + (size_t)(b * LA_H + h) * LA_D;
   float acc[LA_D], zd = 0.f;
 #pragma unroll
   for (int d = 0; d < LA_D; ++d) acc[d] = 0.f;

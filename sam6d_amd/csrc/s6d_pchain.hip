@@ -67,7 +67,7 @@ struct PchainParams {
   int M;
 };
 
-extern __shared__ __attribute__((aligned(16))) char pc_smem[];
+S6D_DYN_LDS(pc_smem);
 
 template <int MT>
 __global__ __launch_bounds__(256) void pchain_kernel(PchainParams p) {

@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 
 #include "s6d_common.h"
+#include "s6d_mem.h"
 
 namespace s6d {
 
@@ -45,7 +46,7 @@ __device__ __forceinline__ int fps_key_index(unsigned long long key, int ref_bs_
 template <int THREADS, int PPT>
 __global__ __launch_bounds__(THREADS) void fps_reg_kernel(const float *__restrict__ xyz, int N, int M,
                                                          int ref_bs_log2, int32_t *__restrict__ idx) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  S6D_DYN_LDS(smem);
   float *spts = reinterpret_cast<float *>(smem);                               // N*3
   unsigned long long *slots = reinterpret_cast<unsigned long long *>(smem + ((N * 3 * 4 + 15) / 16) * 16);
   constexpr int NW = THREADS / kWave;
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(THREADS) void ball_query_kernel(const float *__rest
                                                             const float *__restrict__ xyz, int N, int M,
                                                             float radius2, int nsample, int centres_per_block,
                                                             int32_t *__restrict__ idx) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  S6D_DYN_LDS(smem);
   float *spts = reinterpret_cast<float *>(smem);
   const int b = blockIdx.y;
   const float *p = xyz + (size_t)b * N * 3;

@@ -8,6 +8,7 @@
 // The reference funnels B*6000 3x3 matrices through torch.svd; here every hypothesis is one
 // lane doing a Jacobi eigen-solve in registers (fp64: 78 TF/s on MI355X makes it free).
 #include "s6d_common.h"
+#include "s6d_mem.h"
 #include "s6d_rot.h"
 
 namespace s6d {
@@ -104,7 +105,7 @@ template <int THREADS>
 __global__ __launch_bounds__(THREADS) void transform_min_dist_kernel(
     const float *__restrict__ pts, const float *__restrict__ R, const float *__restrict__ t,
     const float *__restrict__ model, int N, int P, int Nm, float *__restrict__ dmin) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  S6D_DYN_LDS(smem);
   const int Np = (Nm + 3) & ~3;
   float *sx = reinterpret_cast<float *>(smem), *sy = sx + Np, *sz = sy + Np;
   const int b = blockIdx.z, p = blockIdx.y;

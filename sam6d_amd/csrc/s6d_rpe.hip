@@ -9,6 +9,7 @@
 // head dot-products are folded with a 7-shuffle butterfly, softmax and P.V stay in the wave
 // (scores in LDS).  HBM-bound on the embedding: N*256*4 B per row.
 #include "s6d_common.h"
+#include "s6d_mem.h"
 
 namespace s6d {
 
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(WAVES * 64) void rpe_attention_kernel(
   // tensors of their own, or column blocks of the SAME projection output as q | k | v (round 4: W_p folded into the projection)
   // ldq / ldk / ldv: row strides (floats) of q / k / v -- 256 for contiguous tensors, the projection's row width when they are the
   // column blocks of one q | k | v (k | v) projection output (no .contiguous() copies between the Linear and the attention)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  S6D_DYN_LDS(smem);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int Np = (M + 3) & ~3;
   float *sc = reinterpret_cast<float *>(smem) + (size_t)wave * 4 * Np;   // [4][Np] scores of this wave

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void img2tok_kernel(const u16 *__restrict__
 #define S6D_SD_CHANPERM 1            // 0: channel = 16 nt + i with 8-byte residual loads / stores (rounds 2-5; same-box A/B builds)
 #endif
   auto chan = [](int nt, int i) { return S6D_SD_CHANPERM ? 32 * (nt >> 1) + 8 * (i >> 2) + 4 * (nt & 1) + (i & 3) : 16 * nt + i; };
-  extern __shared__ __attribute__((aligned(16))) char sd_smem[];
+  S6D_DYN_LDS(sd_smem);
   u16 *Kl = reinterpret_cast<u16 *>(sd_smem);                       // [64][KROWL]
   u16 *Vl = Kl + kSdJ * KROWL;                                      // [256][kSdVRow]
   float *pl = reinterpret_cast<float *>(Vl + kSdC * kSdVRow);       // [3][256]: obias, gamma, beta
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(kT2IWaves * 64) void tok2img_kernel(const float *__
                                                                 int ld, int k_off, int v_off, long kv_bstride,
                                                                 const u16 *__restrict__ k_pe, int N, float scale,
                                                                 float *__restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) char t2i_smem[];
+  S6D_DYN_LDS(t2i_smem);
   float (*part)[64][18] = reinterpret_cast<float (*)[64][18]>(t2i_smem);   // [wave][lane][m, l, acc[16]]: 72 KB
   const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   u16 *tile = reinterpret_cast<u16 *>(t2i_smem + (size_t)kT2IWaves * 64 * 18 * 4) + (size_t)wave * kT2ITile * kT2IRow;
@@ -510,7 +510,7 @@ constexpr int kT2RLds = kT2RTile * (kT2RKRow + kT2RVRow) * 2;
 __global__ __launch_bounds__(256, 2) void tok2img_raw_kernel(const u16 *__restrict__ qp, const u16 *__restrict__ x, int ld,
                                                             long x_bstride, const u16 *__restrict__ pe, int N,
                                                             float *__restrict__ y) {
-  extern __shared__ __attribute__((aligned(16))) char t2r_smem[];
+  S6D_DYN_LDS(t2r_smem);
   u16 *Kl = reinterpret_cast<u16 *>(t2r_smem);                      // [64][kT2RKRow]  x + pe
   u16 *Vl = Kl + kT2RTile * kT2RKRow;                               // [64][kT2RVRow]  x
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;

@@ -78,7 +78,7 @@ struct SamtokPost {
   u16 *vpt_out;               // (B,256,64) bf16
 };
 
-extern __shared__ __attribute__((aligned(16))) char tk_smem[];
+S6D_DYN_LDS(tk_smem);
 
 // ---- shared pieces (one translation unit, both kernels) ---------------------------------------------------------------------
 // acc[nt] += X W^T for NT tiles of 32 output channels starting at tile `tile0 + NT * wave`... the caller passes the wave's first tile.

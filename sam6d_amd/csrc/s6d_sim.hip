@@ -28,6 +28,7 @@
 // 1e-12f; instance b of a batch has the bits it has alone; similarity(f2, f1) is the transpose of similarity(f1, f2) bit for bit
 // (the same terms in the same order, the products commute).
 #include "s6d_common.h"
+#include "s6d_mem.h"
 
 namespace s6d {
 
@@ -68,7 +69,7 @@ __device__ __forceinline__ float sim_div(float a, float b) {
 __global__ __launch_bounds__(SIM_THREADS) void cosine_sim_kernel(const float *__restrict__ f1, const float *__restrict__ f2, int M1,
                                                                 int M2, int C, int nb, int panels, float temp,
                                                                 float *__restrict__ atten) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  S6D_DYN_LDS(smem);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x / panels, r0 = (blockIdx.x % panels) * SIM_ROWS;
   const int S = C + 2;

@@ -17,7 +17,6 @@ OUT = os.path.join(HERE, "host_cc", "_build")
 EXTRA = os.environ.get("HIPEMU_EXTRA", "").split()
 SO = os.path.join(OUT, "libsam6d_emu" + ("_" + re.sub(r"[^A-Za-z0-9]+", "_", "".join(EXTRA)) if EXTRA else "") + ".so")
 CXX = os.environ.get("HIPEMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-DYN_NAMES = ("smem", "ps_smem", "sd_smem", "t2i_smem", "t2r_smem", "gemm_smem", "fm_smem", "cs_smem", "pc_smem", "tk_smem")
 
 _lib = None
 
@@ -38,20 +37,12 @@ def build(force=False, files=None):
     for f in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
         if files is not None and os.path.basename(f) not in files:
             continue
-        text = open(f).read()
-        # dynamic LDS: `extern __shared__ ... char name[];` refers to a global array defined below (headers that hold kernels,
-        # csrc/s6d_attn_*.h, declare it through a macro keyed on HIPEMU: only .hip text is rewritten here)
-        text = text.replace("extern __shared__", "extern")
-        dst = os.path.join(OUT, os.path.basename(f)[:-4] + ".cc")
+        dst = os.path.join(OUT, os.path.basename(f)[:-4] + ".cc")              # the text itself is not touched
         with open(dst, "w") as g:
-            g.write(f'#line 1 "{f}"\n' + text)
+            g.write(f'#line 1 "{f}"\n' + open(f).read())
         srcs.append(dst)
-    dyn = os.path.join(OUT, "_dyn_shared.cc")
-    with open(dyn, "w") as g:
-        g.write("namespace s6d {\n" + "".join(f"alignas(64) char {n}[160 * 1024];\n" for n in DYN_NAMES) + "}\n"
-                "namespace s6d_h {\nalignas(64) char smem[160 * 1024];\n}\n")
     cmd = [CXX, "-O2", "-std=c++17", "-fPIC", "-shared", "-w", "-ffp-contract=off"] + EXTRA + ["-I", EMU, "-I", CSRC, "-I",
-           os.path.join(REPO, "include"), "-o", SO, os.path.join(EMU, "hipemu.cc"), dyn] + srcs
+           os.path.join(REPO, "include"), "-o", SO, os.path.join(EMU, "hipemu.cc")] + srcs
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         raise RuntimeError("hipemu build failed:\n" + r.stderr[-6000:])

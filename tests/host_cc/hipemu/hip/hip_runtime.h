@@ -4,7 +4,7 @@
 // Execution model: hipLaunchKernelGGL runs the grid one block at a time; the lanes of a block are fibers (hand-rolled stack switch) on one
 // OS thread, scheduled round-robin; __syncthreads and the wave collectives (__shfl*, __ballot, MFMA, ds_read_tr16_b64) are
 // rendezvous points of the block / of a 64-lane wave.  __shared__ variables are function-local statics (one block runs at a
-// time); dynamic shared memory (`extern __shared__ char name[]`) is a global array the build step points the declaration at.
+// time); dynamic shared memory is one host buffer that S6D_DYN_LDS(name) of csrc/s6d_mem.h defines and binds every kernel's name to.
 // MFMA and the transposing LDS read follow the gfx950 lane layouts the kernels were written against (the latter verified
 // with tools/probes/trprobe.hip on the GPU).  Accumulation order inside an emulated MFMA is k-ascending in float32 -- the
 // hardware's internal order is not documented, so parity tests built on this use tolerances, not bit equality, for MFMA
@@ -98,7 +98,6 @@ struct Block {
 };
 
 extern Block *g_blk;
-extern size_t g_dyn_shared_bytes;
 
 inline Lane &self() { return g_blk->lanes[g_blk->cur]; }
 inline int flat_tid() {

@@ -4,7 +4,6 @@
 namespace hipemu {
 
 Block *g_blk = nullptr;
-size_t g_dyn_shared_bytes = 0;
 static const size_t kStack = 256 * 1024;
 
 [[noreturn]] static void die(const char *what) {
@@ -151,7 +150,7 @@ static void run_block(Block &b) {
 void run_grid(dim3 grid, dim3 block, size_t shmem, std::function<void()> body) {
   if (g_blk) die("nested launch");
   static Block b;   // keeps the fiber stacks between launches
-  g_dyn_shared_bytes = shmem;
+  (void)shmem;   // dynamic LDS is the kernel sources' own buffer (S6D_DYN_LDS, csrc/s6d_mem.h): all of a CU's, whatever is asked for
   b.bdim = block;
   b.gdim = grid;
   b.body = body;

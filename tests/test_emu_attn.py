@@ -144,17 +144,22 @@ def test_float16_seq_attention_head_major_on_the_emulator(emu):
 
 def test_kernel_sources_use_the_emulator_macros():
     """A wave rendezvous is S6D_WAVE_RENDEZVOUS() (csrc/s6d_common.h) in every source: the old `// hipemu: wave rendezvous` comment is
-    transformed by nothing any more and would silently be no barrier.  tests/hipemu.py rewrites `extern __shared__` in .hip text only,
-    so a header that holds kernels declares its dynamic LDS through S6D_ATTN_DYN_LDS(), never bare."""
+    transformed by nothing any more and would silently be no barrier.  The emulator rewrites no source text: dynamic LDS, the address
+    spaces and the LDS-DMA are spelled in csrc/s6d_mem.h alone, which says what each is on the emulator, and only that header and
+    s6d_common.h (the rendezvous) name the emulator -- in any file of csrc/, headers and the generated .inc included."""
     import glob
     import os
-    import re
 
     from tests import hipemu
-    for f in glob.glob(os.path.join(hipemu.CSRC, "*.h")) + glob.glob(os.path.join(hipemu.CSRC, "*.hip")):
-        text = open(f).read()
+    files = [f for f in glob.glob(os.path.join(hipemu.CSRC, "*")) if os.path.isfile(f)]
+    assert len(files) > 40 and any(f.endswith("s6d_mem.h") for f in files)
+    for f in files:
+        text, name = open(f).read(), os.path.basename(f)
         assert "hipemu: wave rendezvous" not in text, f
-        assert not (f.endswith(".h") and re.search(r"^\s*extern __shared__", text, flags=re.M)), f
+        if name != "s6d_mem.h":
+            for spelled_out in ("extern __shared__", "address_space(", "__builtin_amdgcn_global_load_lds"):
+                assert spelled_out not in text, (f, spelled_out)
+        assert "hipemu::" not in text or name in ("s6d_mem.h", "s6d_common.h"), f
 
 
 def test_pem_vit_fused_half_pipeline_on_the_emulator(emu):
