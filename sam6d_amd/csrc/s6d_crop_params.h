@@ -20,6 +20,41 @@ __device__ __forceinline__ int nearest_src(int dst, int in, float inv) {
   return min((int)floorf((float)dst * inv), in - 1);
 }
 
+// The reference's square crop box, get_bbox (Pose_Estimation_Model/utils/data_utils.py:126-160), from the extent of a pixel set:
+// rows [rmin, rmax) and columns [cmin, cmax), the whole frame where the caller finds no set.  The longer side, at most min(H, W),
+// centred on the extent and pushed back inside the frame.  box = [rmin, rmax, cmin, cmax].  Shared by the per-frame mask boxes
+// (s6d_pempre.hip) and the template boxes of the onboarding (s6d_onboard.hip); which pixels form the set is the caller's rule.
+__device__ __forceinline__ void square_box(long rmin, long rmax, long cmin, long cmax, int H, int W, long *box) {
+  const long rb = rmax - rmin, cb = cmax - cmin, lim = H < W ? H : W;
+  long side = rb > cb ? rb : cb;
+  side = side < lim ? side : lim;
+  const long cy = (rmin + rmax) / 2, cx = (cmin + cmax) / 2, half = side / 2;
+  rmin = cy - half;
+  rmax = cy + half;
+  cmin = cx - half;
+  cmax = cx + half;
+  if (rmin < 0) {
+    rmax -= rmin;
+    rmin = 0;
+  }
+  if (cmin < 0) {
+    cmax -= cmin;
+    cmin = 0;
+  }
+  if (rmax > H) {
+    rmin -= rmax - H;
+    rmax = H;
+  }
+  if (cmax > W) {
+    cmin -= cmax - W;
+    cmax = W;
+  }
+  box[0] = rmin;
+  box[1] = rmax;
+  box[2] = cmin;
+  box[3] = cmax;
+}
+
 static_assert(sizeof(CropParams) == 48, "CropParams is the 12-int record of include/sam6d_hip.h");
 
 }  // namespace s6d

@@ -5,6 +5,8 @@
 // Under reduced precision the reference (autocast) runs LayerNorm in fp32 with a cast copy on either
 // side; here one pass reads x (and the branch output to add), writes the updated residual stream and
 // the normalised activations, with fp32 statistics.  HBM-bound: 2 reads + 2 writes of C bf16 per token.
+#include <type_traits>
+
 #include "s6d_bf16.h"
 
 namespace s6d {
@@ -40,30 +42,26 @@ __device__ __forceinline__ u16 f2elem(float f) {
   return f2bf_(f);
 }
 
-// one wavefront per token row; VEC chunks of 8 bf16 (16 B) per lane: C <= 64*8*VEC
+// ---- the row pass of the wave-per-row kernels of this file: lane `lane` holds chunk ch = lane + 64 i (8 elements, 16 bytes) of a
+// row in v[i], VEC chunks in all (C <= 64 * 8 * VEC); a chunk at or beyond nchunk = C / 8 is zeros.  The helpers take the BASE
+// pointers and the row's offset `off`, so that the tests of `delta` and `x_out` are tests of the kernel's arguments.
+// (a) load, optional residual add in the element format (written to x_out: the residual stream stays 2-byte), conversion, and the
+// lane's share of the row sum
 template <int VEC, bool F16>
-__global__ __launch_bounds__(256) void add_layernorm_kernel(const u16 *__restrict__ x, const u16 *__restrict__ delta,
-                                                           const float *__restrict__ gamma,
-                                                           const float *__restrict__ beta, float eps, long rows,
-                                                           int C, u16 *__restrict__ x_out, u16 *__restrict__ y_out,
-                                                           float *__restrict__ y_f32) {
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  const int nchunk = C / 8;
-  float v[VEC][8];
+__device__ __forceinline__ float row_load_sum(const u16 *__restrict__ x, const u16 *__restrict__ delta, u16 *__restrict__ x_out,
+                                              long off, int lane, int nchunk, float (&v)[VEC][8]) {
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     const int ch = lane + i * 64;
     if (ch < nchunk) {
       union { uint4 u; u16 h[8]; } a, d;
-      a.u = *reinterpret_cast<const uint4 *>(x + row * C + ch * 8);
+      a.u = *reinterpret_cast<const uint4 *>(x + off + ch * 8);
       if (delta) {
-        d.u = *reinterpret_cast<const uint4 *>(delta + row * C + ch * 8);
+        d.u = *reinterpret_cast<const uint4 *>(delta + off + ch * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a.h[e] = f2elem<F16>(elem2f<F16>(a.h[e]) + elem2f<F16>(d.h[e]));   // residual stream stays bf16
-        if (x_out) *reinterpret_cast<uint4 *>(x_out + row * C + ch * 8) = a.u;
+        for (int e = 0; e < 8; ++e) a.h[e] = f2elem<F16>(elem2f<F16>(a.h[e]) + elem2f<F16>(d.h[e]));
+        if (x_out) *reinterpret_cast<uint4 *>(x_out + off + ch * 8) = a.u;
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -75,7 +73,12 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const u16 *__restric
       for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
     }
   }
-  const float mean = wave_sum(sum) / (float)C;
+  return sum;
+}
+
+// (b) the lane's share of the sum of squared deviations from the row mean
+template <int VEC>
+__device__ __forceinline__ float row_sq_dev(const float (&v)[VEC][8], float mean, int lane, int nchunk) {
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
@@ -88,16 +91,39 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const u16 *__restric
       }
     }
   }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
+  return sq;
+}
+
+// (c) gamma and beta of chunk ch
+__device__ __forceinline__ void row_affine(const float *__restrict__ gamma, const float *__restrict__ beta, int ch, float *gg,
+                                           float *bb) {
+  const float4 g0 = *reinterpret_cast<const float4 *>(gamma + ch * 8), g1 = *reinterpret_cast<const float4 *>(gamma + ch * 8 + 4);
+  const float4 b0 = *reinterpret_cast<const float4 *>(beta + ch * 8), b1 = *reinterpret_cast<const float4 *>(beta + ch * 8 + 4);
+  gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w; gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;
+  bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w; bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
+}
+
+// one wavefront per token row; VEC chunks of 8 bf16 (16 B) per lane: C <= 64*8*VEC
+template <int VEC, bool F16>
+__global__ __launch_bounds__(256) void add_layernorm_kernel(const u16 *__restrict__ x, const u16 *__restrict__ delta,
+                                                           const float *__restrict__ gamma,
+                                                           const float *__restrict__ beta, float eps, long rows,
+                                                           int C, u16 *__restrict__ x_out, u16 *__restrict__ y_out,
+                                                           float *__restrict__ y_f32) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const int nchunk = C / 8;
+  float v[VEC][8];
+  const float mean = wave_sum(row_load_sum<VEC, F16>(x, delta, x_out, row * C, lane, nchunk, v)) / (float)C;
+  const float rstd = rsqrtf(wave_sum(row_sq_dev<VEC>(v, mean, lane, nchunk)) / (float)C + eps);
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     const int ch = lane + i * 64;
     if (ch < nchunk) {
       union { uint4 u; u16 h[8]; } o;
-      const float4 g0 = *reinterpret_cast<const float4 *>(gamma + ch * 8), g1 = *reinterpret_cast<const float4 *>(gamma + ch * 8 + 4);
-      const float4 b0 = *reinterpret_cast<const float4 *>(beta + ch * 8), b1 = *reinterpret_cast<const float4 *>(beta + ch * 8 + 4);
-      const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-      const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+      float gg[8], bb[8];
+      row_affine(gamma, beta, ch, gg, bb);
       if (y_f32) {                                     // fp32 result (the SAM neck's last LayerNorm2d: the encoder's output)
         float4 o0, o1;
         o0.x = (v[i][0] - mean) * rstd * gg[0] + bb[0]; o0.y = (v[i][1] - mean) * rstd * gg[1] + bb[1];
@@ -132,52 +158,15 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const u16 *__restric
   const int lane = threadIdx.x & 63;
   const int nchunk = C / 8;
   float v[VEC][8];
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    const int ch = lane + i * 64;
-    if (ch < nchunk) {
-      union { uint4 u; u16 h[8]; } a, d;
-      a.u = *reinterpret_cast<const uint4 *>(x + row * C + ch * 8);
-      if (delta) {                                      // residual add folded in, as add_layernorm_kernel
-        d.u = *reinterpret_cast<const uint4 *>(delta + row * C + ch * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a.h[e] = f2bf_(bf16_value(a.h[e]) + bf16_value(d.h[e]));
-        if (x_out) *reinterpret_cast<uint4 *>(x_out + row * C + ch * 8) = a.u;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        v[i][e] = bf16_value(a.h[e]);
-        sum += v[i][e];
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
-    }
-  }
-  const float mean = wave_sum(sum) / (float)C;
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    const int ch = lane + i * 64;
-    if (ch < nchunk) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float d = v[i][e] - mean;
-        sq += d * d;
-      }
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
+  const float mean = wave_sum(row_load_sum<VEC, false>(x, delta, x_out, row * C, lane, nchunk, v)) / (float)C;   // the bf16 rows of add_layernorm_kernel
+  const float rstd = rsqrtf(wave_sum(row_sq_dev<VEC>(v, mean, lane, nchunk)) / (float)C + eps);
   float amax = 0.f;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     const int ch = lane + i * 64;
     if (ch < nchunk) {
-      const float4 g0 = *reinterpret_cast<const float4 *>(gamma + ch * 8), g1 = *reinterpret_cast<const float4 *>(gamma + ch * 8 + 4);
-      const float4 b0 = *reinterpret_cast<const float4 *>(beta + ch * 8), b1 = *reinterpret_cast<const float4 *>(beta + ch * 8 + 4);
-      const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-      const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+      float gg[8], bb[8];
+      row_affine(gamma, beta, ch, gg, bb);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         v[i][e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
@@ -293,19 +282,7 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const u16 *__restrict__ 
     }
   }
   const float mean = wave_sum(sum) / (float)C;
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    const int ch = lane + i * 64;
-    if (ch < nchunk) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float d = v[i][e] - mean;
-        sq += d * d;
-      }
-    }
-  }
-  const float sigma = sqrtf(wave_sum(sq) / (float)C + eps);
+  const float sigma = sqrtf(wave_sum(row_sq_dev<VEC>(v, mean, lane, nchunk)) / (float)C + eps);
   if (lane == 0) *reinterpret_cast<float2 *>(out + row * 2) = make_float2(mean, sigma);
 }
 
@@ -328,24 +305,43 @@ extern "C" int s6d_ln_stats_finalize(const float *stats_partial, int groups, int
   return launch_status();
 }
 
-extern "C" int s6d_row_stats_bf16(const void *x, long ldx, long M, int C, float eps, float *row_stats, void *stream) {
-  if (M < 0 || C <= 0 || (C % 8) || ldx < C || (ldx % 8)) return S6D_EINVAL;
-  if (C > 64 * 8 * 3) return S6D_EUNSUPPORTED;
-  if (M == 0) return S6D_OK;
-  if (!x || !row_stats || ((uintptr_t)x & 15) || ((uintptr_t)row_stats & 7)) return S6D_EINVAL;
-  const dim3 grid((unsigned)((M + 3) / 4));
-  const int vec = (C + 511) / 512;
-  if (vec == 1)
-    hipLaunchKernelGGL(row_stats_kernel<1>, grid, dim3(256), 0, as_stream(stream), (const u16 *)x, ldx, M, C, eps, row_stats);
-  else if (vec == 2)
-    hipLaunchKernelGGL(row_stats_kernel<2>, grid, dim3(256), 0, as_stream(stream), (const u16 *)x, ldx, M, C, eps, row_stats);
-  else
-    hipLaunchKernelGGL(row_stats_kernel<3>, grid, dim3(256), 0, as_stream(stream), (const u16 *)x, ldx, M, C, eps, row_stats);
+// The wave-per-row kernels hold a row in VEC chunks of 8 elements per lane; this is the one place VEC is chosen from C / 8.
+// launch_rows calls launch(integral_constant<int, VEC>) for the kernel family of its caller, whose widest instantiation is MAXV.
+static int row_vec(int C) { return (C / 8 + 63) / 64; }
+
+template <int MAXV, class F>
+static int launch_rows(int C, F launch) {
+  const int vec = row_vec(C);
+  if (vec > MAXV) return S6D_EUNSUPPORTED;
+  if (vec == 1) launch(std::integral_constant<int, 1>{});
+  else if (vec == 2) launch(std::integral_constant<int, 2>{});
+  else if (vec == 3) launch(std::integral_constant<int, 3>{});
+  else if constexpr (MAXV >= 4) launch(std::integral_constant<int, 4>{});
   return launch_status();
 }
 
+extern "C" int s6d_row_stats_bf16(const void *x, long ldx, long M, int C, float eps, float *row_stats, void *stream) {
+  if (M < 0 || C <= 0 || (C % 8) || ldx < C || (ldx % 8)) return S6D_EINVAL;
+  if (row_vec(C) > 3) return S6D_EUNSUPPORTED;
+  if (M == 0) return S6D_OK;
+  if (!x || !row_stats || ((uintptr_t)x & 15) || ((uintptr_t)row_stats & 7)) return S6D_EINVAL;
+  return launch_rows<3>(C, [&](auto V) {
+    hipLaunchKernelGGL(row_stats_kernel<decltype(V)::value>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       (const u16 *)x, ldx, M, C, eps, row_stats);
+  });
+}
+
 static int ln_launch(const void *x, const void *delta, const float *gamma, const float *beta, float eps, long rows, int C,
-                     void *x_out, void *y_out, float *y_f32, void *stream, bool f16 = false);
+                     void *x_out, void *y_out, float *y_f32, void *stream, bool f16 = false) {
+  if (rows < 0 || C <= 0 || (C % 8) != 0) return S6D_EINVAL;
+  if (rows == 0) return S6D_OK;
+  if (!x || !gamma || !beta || (delta && !x_out)) return S6D_EINVAL;
+  return launch_rows<4>(C, [&](auto V) {
+    const auto kernel = f16 ? add_layernorm_kernel<decltype(V)::value, true> : add_layernorm_kernel<decltype(V)::value, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, as_stream(stream), (const u16 *)x, (const u16 *)delta,
+                       gamma, beta, eps, rows, C, (u16 *)x_out, (u16 *)y_out, y_f32);
+  });
+}
 
 extern "C" int s6d_add_layernorm_f16(const void *x, const void *delta, const float *gamma, const float *beta,
                                      float eps, long rows, int C, void *x_out, void *y_out, void *stream) {
@@ -365,56 +361,18 @@ extern "C" int s6d_layernorm_bf16_f32(const void *x, const float *gamma, const f
   return ln_launch(x, nullptr, gamma, beta, eps, rows, C, nullptr, nullptr, y_f32, stream);
 }
 
-static int ln_launch(const void *x, const void *delta, const float *gamma, const float *beta, float eps, long rows, int C,
-                     void *x_out, void *y_out, float *y_f32, void *stream, bool f16) {
-  if (rows < 0 || C <= 0 || (C % 8) != 0) return S6D_EINVAL;
-  if (rows == 0) return S6D_OK;
-  if (!x || !gamma || !beta || (delta && !x_out)) return S6D_EINVAL;
-  const unsigned grid = (unsigned)((rows + 3) / 4);
-  const int nchunk = C / 8;
-  hipStream_t st = as_stream(stream);
-#define S6D_LN(V)                                                                                              \
-  do {                                                                                                         \
-    if (f16)                                                                                                   \
-      hipLaunchKernelGGL((add_layernorm_kernel<V, true>), dim3(grid), dim3(256), 0, st, (const u16 *)x, (const u16 *)delta, \
-                         gamma, beta, eps, rows, C, (u16 *)x_out, (u16 *)y_out, y_f32);                        \
-    else                                                                                                       \
-      hipLaunchKernelGGL((add_layernorm_kernel<V, false>), dim3(grid), dim3(256), 0, st, (const u16 *)x, (const u16 *)delta, \
-                         gamma, beta, eps, rows, C, (u16 *)x_out, (u16 *)y_out, y_f32);                        \
-  } while (0)
-  if (nchunk <= 64) S6D_LN(1);
-  else if (nchunk <= 128) S6D_LN(2);
-  else if (nchunk <= 192) S6D_LN(3);
-  else if (nchunk <= 256) S6D_LN(4);
-  else return S6D_EUNSUPPORTED;
-#undef S6D_LN
-  return launch_status();
-}
-
-extern "C" int s6d_add_layernorm_fp8(const void *x, const void *delta, const float *gamma, const float *beta, float eps, long rows,
-                                     int C, void *x_out, void *y8, unsigned char *yscale, void *stream);
-
-extern "C" int s6d_layernorm_fp8(const void *x, const float *gamma, const float *beta, float eps, long rows, int C, void *y8,
-                                 unsigned char *yscale, void *stream) {
-  return s6d_add_layernorm_fp8(x, nullptr, gamma, beta, eps, rows, C, nullptr, y8, yscale, stream);
-}
-
 extern "C" int s6d_add_layernorm_fp8(const void *x, const void *delta, const float *gamma, const float *beta, float eps, long rows,
                                      int C, void *x_out, void *y8, unsigned char *yscale, void *stream) {
   if (rows < 0 || C <= 0 || (C % 8) != 0) return S6D_EINVAL;
   if (rows == 0) return S6D_OK;
   if (!x || !gamma || !beta || !y8 || !yscale || (delta && !x_out)) return S6D_EINVAL;
-  const unsigned grid = (unsigned)((rows + 3) / 4);
-  const int nchunk = C / 8;
-  hipStream_t st = as_stream(stream);
-#define S6D_LN8(V)                                                                                              \
-  hipLaunchKernelGGL((layernorm_fp8_kernel<V>), dim3(grid), dim3(256), 0, st, (const u16 *)x, (const u16 *)delta, gamma, beta, \
-                     eps, rows, C, (u16 *)x_out, (unsigned char *)y8, yscale)
-  if (nchunk <= 64) S6D_LN8(1);
-  else if (nchunk <= 128) S6D_LN8(2);
-  else if (nchunk <= 192) S6D_LN8(3);
-  else if (nchunk <= 256) S6D_LN8(4);
-  else return S6D_EUNSUPPORTED;
-#undef S6D_LN8
-  return launch_status();
+  return launch_rows<4>(C, [&](auto V) {
+    hipLaunchKernelGGL(layernorm_fp8_kernel<decltype(V)::value>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       (const u16 *)x, (const u16 *)delta, gamma, beta, eps, rows, C, (u16 *)x_out, (unsigned char *)y8, yscale);
+  });
+}
+
+extern "C" int s6d_layernorm_fp8(const void *x, const float *gamma, const float *beta, float eps, long rows, int C, void *y8,
+                                 unsigned char *yscale, void *stream) {
+  return s6d_add_layernorm_fp8(x, nullptr, gamma, beta, eps, rows, C, nullptr, y8, yscale, stream);
 }

@@ -68,36 +68,8 @@ __global__ __launch_bounds__(kCmpThreads) void template_boxes_kernel(const unsig
       for (int k = 0; k < 8; ++k) r[k] = max(r[k], s_b[k][w]);
     }
     const bool ok = c > 0;
-    long rmin = ok ? -r[0] : 0, rmax = ok ? r[1] + 1 : H, cmin = ok ? -r[2] : 0, cmax = ok ? r[3] + 1 : W;
-    const long rb = rmax - rmin, cb = cmax - cmin, lim = H < W ? H : W;
-    long side = rb > cb ? rb : cb;
-    side = side < lim ? side : lim;
-    const long cy = (rmin + rmax) / 2, cx = (cmin + cmax) / 2, half = side / 2;
-    rmin = cy - half;
-    rmax = cy + half;
-    cmin = cx - half;
-    cmax = cx + half;
-    if (rmin < 0) {
-      rmax -= rmin;
-      rmin = 0;
-    }
-    if (cmin < 0) {
-      cmax -= cmin;
-      cmin = 0;
-    }
-    if (rmax > H) {
-      rmin -= rmax - H;
-      rmax = H;
-    }
-    if (cmax > W) {
-      cmin -= cmax - W;
-      cmax = W;
-    }
     cnt_out[t] = c;
-    box[t * 4 + 0] = rmin;
-    box[t * 4 + 1] = rmax;
-    box[t * 4 + 2] = cmin;
-    box[t * 4 + 3] = cmax;
+    square_box(ok ? -r[0] : 0, ok ? r[1] + 1 : H, ok ? -r[2] : 0, ok ? r[3] + 1 : W, H, W, box + t * 4);
     const bool any = r[5] >= 0;
     tight[t * 4 + 0] = any ? -r[6] : 0;
     tight[t * 4 + 1] = any ? -r[4] : 0;

@@ -24,6 +24,7 @@
 //   radius_filter    ``flag = norm(cloud - center) < radius * 1.2`` (:214-221) and the second in-order compaction, in place.
 #include "s6d_common.h"
 #include "s6d_compact.h"
+#include "s6d_crop_params.h"
 #include "s6d_cv_resize.h"
 
 namespace s6d {
@@ -81,37 +82,9 @@ __global__ __launch_bounds__(kCmpThreads) void mask_boxes_kernel(const unsigned 
       rx1 = max(rx1, s_x1[w]);
     }
     const bool ok = c > min_points;
-    long rmin = ok ? ry0 : 0, rmax = ok ? ry1 + 1 : H, cmin = ok ? rx0 : 0, cmax = ok ? rx1 + 1 : W;
-    const long rb = rmax - rmin, cb = cmax - cmin, lim = H < W ? H : W;
-    long b = rb > cb ? rb : cb;
-    b = b < lim ? b : lim;
-    const long cy = (rmin + rmax) / 2, cx = (cmin + cmax) / 2, half = b / 2;
-    rmin = cy - half;
-    rmax = cy + half;
-    cmin = cx - half;
-    cmax = cx + half;
-    if (rmin < 0) {
-      rmax -= rmin;
-      rmin = 0;
-    }
-    if (cmin < 0) {
-      cmax -= cmin;
-      cmin = 0;
-    }
-    if (rmax > H) {
-      rmin -= rmax - H;
-      rmax = H;
-    }
-    if (cmax > W) {
-      cmin -= cmax - W;
-      cmax = W;
-    }
     cnt_out[p] = c;
     ok_out[p] = ok ? 1 : 0;
-    box[p * 4 + 0] = rmin;
-    box[p * 4 + 1] = rmax;
-    box[p * 4 + 2] = cmin;
-    box[p * 4 + 3] = cmax;
+    square_box(ok ? ry0 : 0, ok ? ry1 + 1 : H, ok ? rx0 : 0, ok ? rx1 + 1 : W, H, W, box + p * 4);
   }
 }
 

@@ -135,22 +135,50 @@ __device__ __forceinline__ float raster_weights(const RasterTri &tr, const long 
   return (q[0] + q[1]) + q[2];
 }
 
-__device__ __forceinline__ void raster_sample(const RasterTri &tr, int u, int v, int f, unsigned long long *__restrict__ key) {
+// The coverage pass is one pair of kernels over two policies.  KEY: the word a covered sample leaves in the per-pixel minimum and
+// how it is made from (Z, face).  CAM: where the camera of view t comes from.
+struct RasterKeyFace {                                                   // the template render: visibility key of the header
+  typedef unsigned long long word;
+  static __device__ __forceinline__ word make(float z, int f) {
+    return ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)(unsigned)f;
+  }
+};
+struct RasterKeyDepth {                                                  // the depth render: bits(Z) alone
+  typedef unsigned word;
+  static __device__ __forceinline__ word make(float z, int) { return __float_as_uint(z); }
+};
+struct RasterOneCam {                                                    // one camera for all views
+  RasterCam c;
+  __device__ __forceinline__ RasterCam view(int) const { return c; }
+};
+struct RasterViewCams {                                                  // cams (T,4) f32 [fx fy cx cy] and one znear
+  const float *cams;
+  float znear;
+  __device__ __forceinline__ RasterCam view(int t) const {
+    const float *k = cams + (size_t)t * 4;
+    return RasterCam{k[0], k[1], k[2], k[3], znear};
+  }
+};
+
+template <class KEY>
+__device__ __forceinline__ void raster_sample(const RasterTri &tr, int u, int v, int f, typename KEY::word *__restrict__ key) {
   long w[3];
   if (!raster_covers(tr, u, v, w)) return;
   float q[3];
   const float z = 1.0f / raster_weights(tr, w, q);
-  atomicMin(key, ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)(unsigned)f);
+  atomicMin(key, KEY::make(z, f));
 }
 
+template <class KEY, class CAM>
 __global__ __launch_bounds__(RASTER_THREADS) void raster_small_kernel(const float *__restrict__ vertices, const int *__restrict__ faces,
                                                                       const float *__restrict__ poses, int V, int F, int T, int H, int W,
-                                                                      RasterCam c, unsigned long long *__restrict__ keys,
+                                                                      CAM cam, typename KEY::word *__restrict__ keys,
                                                                       int *__restrict__ large_list, int *__restrict__ large_count,
                                                                       int *__restrict__ skipped) {
   const long i = (long)blockIdx.x * RASTER_THREADS + threadIdx.x;
   if (i >= (long)T * F) return;
   const int t = (int)(i / F), f = (int)(i - (long)t * F);
+  const RasterCam c = cam.view(t);
   RasterTri tr;
   const int st = raster_setup(vertices, faces, poses, V, t, f, c, H, W, tr);
   if (st < 0) atomicAdd(&skipped[t], 1);
@@ -159,28 +187,30 @@ __global__ __launch_bounds__(RASTER_THREADS) void raster_small_kernel(const floa
     large_list[atomicAdd(large_count, 1)] = (int)i;                      // at most T * F appends: the list's size
     return;
   }
-  unsigned long long *kp = keys + (size_t)t * H * W;
+  typename KEY::word *kp = keys + (size_t)t * H * W;
   for (int v = tr.v0; v <= tr.v1; ++v)
-    for (int u = tr.u0; u <= tr.u1; ++u) raster_sample(tr, u, v, f, kp + (size_t)v * W + u);
+    for (int u = tr.u0; u <= tr.u1; ++u) raster_sample<KEY>(tr, u, v, f, kp + (size_t)v * W + u);
 }
 
+template <class KEY, class CAM>
 __global__ __launch_bounds__(RASTER_THREADS) void raster_large_kernel(const float *__restrict__ vertices, const int *__restrict__ faces,
                                                                       const float *__restrict__ poses, int V, int F, int H, int W,
-                                                                      RasterCam c, unsigned long long *__restrict__ keys,
+                                                                      CAM cam, typename KEY::word *__restrict__ keys,
                                                                       const int *__restrict__ large_list,
                                                                       const int *__restrict__ large_count) {
   const int count = *large_count;
   for (int e = blockIdx.x; e < count; e += gridDim.x) {
     const int i = large_list[e];
     const int t = i / F, f = i - t * F;
+    const RasterCam c = cam.view(t);
     RasterTri tr;                                                        // every lane sets the triangle up: the same values
     if (raster_setup(vertices, faces, poses, V, t, f, c, H, W, tr) <= 0) continue;
     const int bw = tr.u1 - tr.u0 + 1;
     const long n = (long)bw * (tr.v1 - tr.v0 + 1);
-    unsigned long long *kp = keys + (size_t)t * H * W;
+    typename KEY::word *kp = keys + (size_t)t * H * W;
     for (long j = threadIdx.x; j < n; j += RASTER_THREADS) {
       const int r = (int)(j / bw), v = tr.v0 + r, u = tr.u0 + (int)(j - (long)r * bw);
-      raster_sample(tr, u, v, f, kp + (size_t)v * W + u);
+      raster_sample<KEY>(tr, u, v, f, kp + (size_t)v * W + u);
     }
   }
 }
@@ -243,82 +273,53 @@ __global__ __launch_bounds__(RASTER_THREADS) void raster_resolve_kernel(const fl
 }
 
 // ---- depth alone, a camera per view (s6d_raster_depth_f32: the two renders of a VSD evaluation, csrc/s6d_boperr.hip) ----------------
-// The same vertex stage, set-up, coverage rule and depth statement as above, so a pixel holds the depth bits the full render gives
-// it.  The visibility key is bits(Z) alone (Z > 0: the bits order like the value), reduced with atomicMin on unsigned IN the depth
-// output, preset to all ones; a last pass turns what is still all ones into 0.  The workspace is the list of large triangles only.
+// raster_small_kernel / raster_large_kernel<RasterKeyDepth, RasterViewCams>: the kernels of the full render with another key and
+// camera source, so a pixel holds the depth bits the full render gives it.  The key is bits(Z) alone (Z > 0: the bits order like the
+// value), reduced with atomicMin on unsigned IN the depth output, preset to all ones; a last pass turns what is still all ones into 0.
+// The workspace is the list of large triangles only.
 constexpr unsigned RASTER_EMPTY32 = ~0u;
-
-__device__ __forceinline__ RasterCam raster_view_cam(const float *__restrict__ cams, int t, float znear) {
-  const float *k = cams + (size_t)t * 4;
-  return RasterCam{k[0], k[1], k[2], k[3], znear};
-}
-
-__device__ __forceinline__ void raster_sample_depth(const RasterTri &tr, int u, int v, unsigned *__restrict__ key) {
-  long w[3];
-  if (!raster_covers(tr, u, v, w)) return;
-  float q[3];
-  const float z = 1.0f / raster_weights(tr, w, q);
-  atomicMin(key, __float_as_uint(z));
-}
-
-__global__ __launch_bounds__(RASTER_THREADS) void raster_depth_small_kernel(const float *__restrict__ vertices, const int *__restrict__ faces,
-                                                                            const float *__restrict__ poses, const float *__restrict__ cams,
-                                                                            int V, int F, int T, int H, int W, float znear,
-                                                                            unsigned *__restrict__ keys, int *__restrict__ large_list,
-                                                                            int *__restrict__ large_count, int *__restrict__ skipped) {
-  const long i = (long)blockIdx.x * RASTER_THREADS + threadIdx.x;
-  if (i >= (long)T * F) return;
-  const int t = (int)(i / F), f = (int)(i - (long)t * F);
-  const RasterCam c = raster_view_cam(cams, t, znear);
-  RasterTri tr;
-  const int st = raster_setup(vertices, faces, poses, V, t, f, c, H, W, tr);
-  if (st < 0) atomicAdd(&skipped[t], 1);
-  if (st <= 0) return;
-  if ((long)(tr.u1 - tr.u0 + 1) * (tr.v1 - tr.v0 + 1) > RASTER_LARGE_BOX) {
-    large_list[atomicAdd(large_count, 1)] = (int)i;                      // at most T * F appends: the list's size
-    return;
-  }
-  unsigned *kp = keys + (size_t)t * H * W;
-  for (int v = tr.v0; v <= tr.v1; ++v)
-    for (int u = tr.u0; u <= tr.u1; ++u) raster_sample_depth(tr, u, v, kp + (size_t)v * W + u);
-}
-
-__global__ __launch_bounds__(RASTER_THREADS) void raster_depth_large_kernel(const float *__restrict__ vertices, const int *__restrict__ faces,
-                                                                            const float *__restrict__ poses, const float *__restrict__ cams,
-                                                                            int V, int F, int H, int W, float znear,
-                                                                            unsigned *__restrict__ keys, const int *__restrict__ large_list,
-                                                                            const int *__restrict__ large_count) {
-  const int count = *large_count;
-  for (int e = blockIdx.x; e < count; e += gridDim.x) {
-    const int i = large_list[e];
-    const int t = i / F, f = i - t * F;
-    const RasterCam c = raster_view_cam(cams, t, znear);
-    RasterTri tr;
-    if (raster_setup(vertices, faces, poses, V, t, f, c, H, W, tr) <= 0) continue;
-    const int bw = tr.u1 - tr.u0 + 1;
-    const long n = (long)bw * (tr.v1 - tr.v0 + 1);
-    unsigned *kp = keys + (size_t)t * H * W;
-    for (long j = threadIdx.x; j < n; j += RASTER_THREADS) {
-      const int r = (int)(j / bw), v = tr.v0 + r, u = tr.u0 + (int)(j - (long)r * bw);
-      raster_sample_depth(tr, u, v, kp + (size_t)v * W + u);
-    }
-  }
-}
 
 __global__ __launch_bounds__(RASTER_THREADS) void raster_depth_resolve_kernel(unsigned *__restrict__ keys, size_t total) {
   for (size_t p = (size_t)blockIdx.x * RASTER_THREADS + threadIdx.x; p < total; p += (size_t)gridDim.x * RASTER_THREADS)
     if (keys[p] == RASTER_EMPTY32) keys[p] = 0u;                         // the bits of 0.f: background
 }
 
-// workspace of the depth render: list (T F) i32 | the list's length (one i32, padded to 8 bytes)
-__host__ inline long raster_depth_count_offset(int T, int F) { return ((long)T * F * 4 + 7) & ~7L; }
-
-// workspace: keys (T,H,W) u64 | list (T F) i32 | the list's length (one i32, padded to 8 bytes)
+// workspace of the full render: keys (T,H,W) u64 | list (T F) i32 | the list's length (one i32, padded to 8 bytes); of the depth
+// render: the list and its length
+__host__ inline long raster_list_bytes(int T, int F) { return ((long)T * F * 4 + 7) & ~7L; }
 __host__ inline long raster_list_offset(int T, int H, int W) { return (long)T * H * W * 8; }
-__host__ inline long raster_count_offset(int T, int F, int H, int W) { return raster_list_offset(T, H, W) + (((long)T * F * 4 + 7) & ~7L); }
 __host__ inline bool raster_sizes_ok(int V, int F, int T, int H, int W) { return V >= 0 && F >= 0 && T >= 0 && H > 0 && W > 0; }
 __host__ inline bool raster_sizes_supported(int F, int T, int H, int W) {
   return H <= RASTER_MAX_SIDE && W <= RASTER_MAX_SIDE && (long)T * F <= 0x7fffffffL && (long)T * H * W <= (1L << 40);
+}
+__host__ inline unsigned raster_resolve_grid(size_t total) {
+  const size_t g = (total + RASTER_THREADS - 1) / RASTER_THREADS;
+  return (unsigned)(g > 65536 ? 65536 : g);
+}
+
+// What the two renders share up to their resolve pass: keys, the list's length and `skipped` preset, then the coverage launches.
+// `list` points at the list of large triangles, its length follows it.
+template <class KEY, class CAM>
+static int raster_cover(const float *vertices, const int32_t *faces, const float *poses, int V, int F, int T, int H, int W, CAM cam,
+                        typename KEY::word *keys, char *list, int32_t *skipped, hipStream_t s) {
+  int *count = reinterpret_cast<int *>(list + raster_list_bytes(T, F));
+  hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)T * H * W * sizeof(typename KEY::word), s);
+  if (e == hipSuccess) e = hipMemsetAsync(count, 0, 8, s);
+  if (e == hipSuccess) e = hipMemsetAsync(skipped, 0, (size_t)T * 4, s);
+  if (e != hipSuccess) {
+    set_hip_error(e);
+    return S6D_ELAUNCH;
+  }
+  const long pairs = (long)T * F;
+  if (pairs == 0) return S6D_OK;
+  hipLaunchKernelGGL((raster_small_kernel<KEY, CAM>), dim3((unsigned)((pairs + RASTER_THREADS - 1) / RASTER_THREADS)),
+                     dim3(RASTER_THREADS), 0, s, vertices, faces, poses, V, F, T, H, W, cam, keys, reinterpret_cast<int *>(list), count,
+                     skipped);
+  const int rc = launch_status();
+  if (rc != S6D_OK) return rc;
+  hipLaunchKernelGGL((raster_large_kernel<KEY, CAM>), dim3((unsigned)(pairs < RASTER_LARGE_GRID ? pairs : RASTER_LARGE_GRID)),
+                     dim3(RASTER_THREADS), 0, s, vertices, faces, poses, V, F, H, W, cam, keys, reinterpret_cast<int *>(list), count);
+  return launch_status();
 }
 
 }  // namespace s6d
@@ -327,7 +328,7 @@ using namespace s6d;
 
 extern "C" long s6d_raster_workspace_bytes(int T, int F, int H, int W) {
   if (!raster_sizes_ok(0, F, T, H, W) || !raster_sizes_supported(F, T, H, W)) return -1;
-  return raster_count_offset(T, F, H, W) + 8;
+  return raster_list_offset(T, H, W) + raster_list_bytes(T, F) + 8;
 }
 
 extern "C" int s6d_raster_views_f32(const float *vertices, const int32_t *faces, const unsigned char *colors, const float *poses, int V,
@@ -347,38 +348,17 @@ extern "C" int s6d_raster_views_f32(const float *vertices, const int32_t *faces,
   hipStream_t s = as_stream(stream);
   char *ws = reinterpret_cast<char *>(workspace);
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws);
-  int *list = reinterpret_cast<int *>(ws + raster_list_offset(T, H, W));
-  int *count = reinterpret_cast<int *>(ws + raster_count_offset(T, F, H, W));
-  hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)T * H * W * 8, s);
-  if (e == hipSuccess) e = hipMemsetAsync(count, 0, 8, s);
-  if (e == hipSuccess) e = hipMemsetAsync(skipped, 0, (size_t)T * 4, s);
-  if (e != hipSuccess) {
-    set_hip_error(e);
-    return S6D_ELAUNCH;
-  }
-  const RasterCam c = {fx, fy, cx, cy, znear};
-  const long pairs = (long)T * F;
-  if (pairs > 0) {
-    hipLaunchKernelGGL(raster_small_kernel, dim3((unsigned)((pairs + RASTER_THREADS - 1) / RASTER_THREADS)), dim3(RASTER_THREADS), 0, s,
-                       vertices, faces, poses, V, F, T, H, W, c, keys, list, count, skipped);
-    const int rc = launch_status();
-    if (rc != S6D_OK) return rc;
-    hipLaunchKernelGGL(raster_large_kernel, dim3((unsigned)(pairs < RASTER_LARGE_GRID ? pairs : RASTER_LARGE_GRID)), dim3(RASTER_THREADS),
-                       0, s, vertices, faces, poses, V, F, H, W, c, keys, list, count);
-    const int rc2 = launch_status();
-    if (rc2 != S6D_OK) return rc2;
-  }
-  const size_t total = (size_t)T * H * W;
-  size_t g = (total + RASTER_THREADS - 1) / RASTER_THREADS;
-  if (g > 65536) g = 65536;
-  hipLaunchKernelGGL(raster_resolve_kernel, dim3((unsigned)g), dim3(RASTER_THREADS), 0, s, vertices, faces, colors, poses, V, T, H, W, c,
-                     ambient, diffuse, keys, rgb, mask, xyz, depth, face);
+  const RasterOneCam cam = {{fx, fy, cx, cy, znear}};
+  const int rc = raster_cover<RasterKeyFace>(vertices, faces, poses, V, F, T, H, W, cam, keys, ws + raster_list_offset(T, H, W), skipped, s);
+  if (rc != S6D_OK) return rc;
+  hipLaunchKernelGGL(raster_resolve_kernel, dim3(raster_resolve_grid((size_t)T * H * W)), dim3(RASTER_THREADS), 0, s, vertices, faces,
+                     colors, poses, V, T, H, W, cam.c, ambient, diffuse, keys, rgb, mask, xyz, depth, face);
   return launch_status();
 }
 
 extern "C" long s6d_raster_depth_workspace_bytes(int T, int F, int H, int W) {
   if (!raster_sizes_ok(0, F, T, H, W) || !raster_sizes_supported(F, T, H, W)) return -1;
-  return raster_depth_count_offset(T, F) + 8;
+  return raster_list_bytes(T, F) + 8;
 }
 
 extern "C" int s6d_raster_depth_f32(const float *vertices, const int32_t *faces, const float *poses, const float *cams, int V, int F,
@@ -390,31 +370,11 @@ extern "C" int s6d_raster_depth_f32(const float *vertices, const int32_t *faces,
   if (!poses || !cams || !workspace || !depth || !skipped || (F > 0 && (!vertices || !faces))) return S6D_EINVAL;
   if ((uintptr_t)workspace & 7) return S6D_EINVAL;
   hipStream_t s = as_stream(stream);
-  char *ws = reinterpret_cast<char *>(workspace);
   unsigned *keys = reinterpret_cast<unsigned *>(depth);
-  int *list = reinterpret_cast<int *>(ws);
-  int *count = reinterpret_cast<int *>(ws + raster_depth_count_offset(T, F));
+  const int rc = raster_cover<RasterKeyDepth>(vertices, faces, poses, V, F, T, H, W, RasterViewCams{cams, znear}, keys,
+                                              reinterpret_cast<char *>(workspace), skipped, s);
+  if (rc != S6D_OK) return rc;
   const size_t total = (size_t)T * H * W;
-  hipError_t e = hipMemsetAsync(keys, 0xff, total * 4, s);
-  if (e == hipSuccess) e = hipMemsetAsync(count, 0, 8, s);
-  if (e == hipSuccess) e = hipMemsetAsync(skipped, 0, (size_t)T * 4, s);
-  if (e != hipSuccess) {
-    set_hip_error(e);
-    return S6D_ELAUNCH;
-  }
-  const long pairs = (long)T * F;
-  if (pairs > 0) {
-    hipLaunchKernelGGL(raster_depth_small_kernel, dim3((unsigned)((pairs + RASTER_THREADS - 1) / RASTER_THREADS)), dim3(RASTER_THREADS), 0,
-                       s, vertices, faces, poses, cams, V, F, T, H, W, znear, keys, list, count, skipped);
-    const int rc = launch_status();
-    if (rc != S6D_OK) return rc;
-    hipLaunchKernelGGL(raster_depth_large_kernel, dim3((unsigned)(pairs < RASTER_LARGE_GRID ? pairs : RASTER_LARGE_GRID)),
-                       dim3(RASTER_THREADS), 0, s, vertices, faces, poses, cams, V, F, H, W, znear, keys, list, count);
-    const int rc2 = launch_status();
-    if (rc2 != S6D_OK) return rc2;
-  }
-  size_t g = (total + RASTER_THREADS - 1) / RASTER_THREADS;
-  if (g > 65536) g = 65536;
-  hipLaunchKernelGGL(raster_depth_resolve_kernel, dim3((unsigned)g), dim3(RASTER_THREADS), 0, s, keys, total);
+  hipLaunchKernelGGL(raster_depth_resolve_kernel, dim3(raster_resolve_grid(total)), dim3(RASTER_THREADS), 0, s, keys, total);
   return launch_status();
 }

@@ -20,6 +20,11 @@ def test_layernorm_fp8_on_the_emulator(emu):
         T.test_layernorm_fp8_vs_library_statement(rows, C)
 
 
+def test_add_layernorm_fp8_on_the_emulator(emu):
+    for rows, C in ((5, 160), (6, 520), (5, 1288), (4, 2048)):
+        T.test_add_layernorm_fp8_is_the_add_then_the_quantiser(rows, C)
+
+
 def _run():
     import ctypes
 

@@ -143,6 +143,25 @@ def test_layernorm_fp8_vs_library_statement(rows, C):
     assert d.max() <= 2.0 ** -4 and ((y8 != q)[same_scale]).float().mean() < 5e-3
 
 
+@pytest.mark.parametrize("rows,C", [(5, 160), (6, 520), (5, 1288), (4, 2048)])
+def test_add_layernorm_fp8_is_the_add_then_the_quantiser(rows, C):
+    """s6d_add_layernorm_fp8 (layernorm_fp8 with a residual), bit for bit: its x_out is add_layernorm's and the bf16 rounding of
+    x + delta, and its (bytes, scales) are layernorm_fp8's of that x_out.  One shape per number of 16-byte chunks a lane holds:
+    C 160 (one chunk, 20 of 64 lanes, 5 rows on workgroups of 4), 520 (two, one lane in the second), 1288 (three, ragged),
+    2048 (four, full)."""
+    from sam6d_amd import ops
+    g = torch.Generator().manual_seed(rows * 10000 + C)
+    x = (torch.randn(rows, C, generator=g) * 3 + 0.5).to(torch.bfloat16)
+    d = (torch.randn(rows, C, generator=g) * 2 - 0.25).to(torch.bfloat16)
+    w = (1 + 0.1 * torch.randn(C, generator=g)).cuda()
+    b = (0.1 * torch.randn(C, generator=g)).cuda()
+    xo, y8, ys = ops.layernorm_fp8(x.cuda(), w, b, 1e-6, delta=d.cuda())
+    assert torch.equal(xo, ops.add_layernorm(x.cuda(), d.cuda(), w, b, 1e-6)[0])
+    assert torch.equal(xo.cpu().view(torch.int16), (x.float() + d.float()).to(torch.bfloat16).view(torch.int16))
+    y8_, ys_ = ops.layernorm_fp8(xo, w, b, 1e-6)
+    assert torch.equal(y8, y8_) and torch.equal(ys, ys_)
+
+
 E_BLOCK_FP8 = 2.1e-2      # profiles/r02_fp8_block_probe.txt: e4m3 operands on ALL FOUR Linear layers of a ViT-H block cost 2.1e-2 of the
                           # block's output rms (bf16 operands: 1.3e-3); this path quantises two of the four (qkv, lin1)
 
