@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 130
+#define S6D_ABI_VERSION 131
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -244,6 +244,43 @@ int s6d_pose_err_mssd_mspd_f32(const float *vertices, const float *est, const fl
 int s6d_vsd_counts_f32(const float *depth_est, const float *depth_gt, const float *depth_test, const int32_t *test_index,
                        const float *cams, const float *scale, int N, int M, int H, int W, float delta, const float *taus_host,
                        int NT, int32_t *uni, int32_t *inter, int32_t *ge, void *stream);
+
+/* ---------------------------------------------------------------- COCO AP of ISM results (csrc/s6d_cocoeval.hip)
+ * The device stages of the detection / segmentation AP as DEFINED in sam6d_amd/evaluation.py: integers for the
+ * masks, one float64 operation chain for the boxes.  pycocotools and bop_toolkit are not part of this project; nothing here claims
+ * equality with their output.  Thresholds and area bounds are float64 and travel in a device buffer: no entry has a `double`
+ * parameter. */
+
+/* masks (N, HW) bytes (a pixel is set when its byte is not 0) -> packed (N, ceil(HW / 64)) 64-bit words, bit k of word j = pixel
+ * 64 j + k (row-major pixel order), the bits past HW zero; area (N) i32 = set pixels.  N >= 0, 1 <= HW < 2^31. */
+int s6d_mask_pack_u8(const uint8_t *masks, int N, long HW, uint64_t *packed, int32_t *area, void *stream);
+
+/* pairs (P,2) i32 = (row of dpacked (Nd, words), row of gpacked (Ng, words)) -> inter (P) i32 = popcount(d & g).  Consecutive
+ * pairs with the same detection row are served by one workgroup per 2048-word chunk that reads the detection's words once.
+ * Integer sums: a pair's count does not depend on P or on the order of the list.  A row outside its array leaves the count 0.
+ * words >= 1, 64 words < 2^31; P > 0 with an empty array is S6D_EINVAL. */
+int s6d_mask_pair_inter(const uint64_t *dpacked, int Nd, const uint64_t *gpacked, int Ng, long words, const int32_t *pairs, int P,
+                        int32_t *inter, void *stream);
+
+/* dboxes (Nd,4), gboxes (Ng,4) f64 = x y w h, pairs (P,2) i32 -> iou (P) f64:  w = min(dx + dw, gx + gw) - max(dx, gx), h
+ * likewise; 0 when w <= 0 or h <= 0, else i = w h, u = (dw dh + gw gh) - i, iou = i / u; every operation rounded on its own (no
+ * fused multiply-add).  A row outside its array gives 0. */
+int s6d_box_pair_iou_f64(const double *dboxes, int Nd, const double *gboxes, int Ng, const int32_t *pairs, int P, double *iou,
+                         void *stream);
+
+/* Greedy matching, one workgroup per group = (image, category), one lane per (threshold, area range).  groups (n_groups,4) i32 =
+ * first detection, detections D, first ground truth, ground truths G <= S6D_COCO_MATCH_MAX_GT; iou_off (n_groups) i64: the group's
+ * (D,G) row-major IoUs begin at ious[iou_off]; det_area (n_det) f64, gt_area (n_gt) f64, gt_ignore (n_gt) bytes; params =
+ * NT thresholds then NA (lo, hi) area bounds, f64 on the device, NT NA <= 64.  The detections of a group are visited in the order
+ * given (the caller sorts by score and truncates).  bar = min(t, 1 - 1e-10); over the unmatched non-ignored ground truths in
+ * input order an IoU >= bar takes the match and becomes the bar; only when none matched, the same over the ignored ones (flagged,
+ * or area outside [lo, hi]).  -> match (n_det, NT, NA) i32: the ground truth's index inside its group or -1; ignore
+ * (n_det, NT, NA) bytes: the match is ignored, or there is none and the detection's area is outside [lo, hi].  Detections outside
+ * every group, and groups that do not fit the arrays, stay at -1 / 0. */
+#define S6D_COCO_MATCH_MAX_GT 64
+int s6d_coco_match(const double *ious, const long *iou_off, const int32_t *groups, const double *det_area, const double *gt_area,
+                   const uint8_t *gt_ignore, const double *params, int n_groups, int NT, int NA, long n_det, long n_gt, long n_iou,
+                   int32_t *match, uint8_t *ignore, void *stream);
 
 /* ---------------------------------------------------------------- PEM pose solvers
  * Replace the library-op chains of Pose_Estimation_Model/utils/model_utils.py. */

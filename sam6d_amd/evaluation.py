@@ -21,13 +21,45 @@ vertices of its evaluation model):
 Every error function goes through ``policy.guard("eval.<name>", ...)``: kernels on device tensors, the torch statements below
 otherwise (policy field ``bop_eval`` = "0", or CPU tensors).  The torch branch is chunked over the symmetries, so it does not
 hold the (N, S, V, 3) tensor either.
+
+COCO AP of ISM results (``coco_scores``).  ``ism/handoff.py`` writes the BOP / COCO detection json; this module
+scores it, by the number the Instance Segmentation Model is published by.  ``pycocotools`` and ``bop_toolkit`` are not part of this
+project: no number is claimed to equal their output, the following IS the definition, and the tests pin the kernels
+(``csrc/s6d_cocoeval.hip``) and the torch statements below to an independent restatement of it (``tests/coco_ref.py``) with `equal`.
+
+  instances   a detection: image index, category (object id), score, and a mask or a box x, y, w, h.  A ground truth: image index,
+              category, visible mask, visible box, an ``ignore`` flag (the loader sets it from visib_fract < 0.1).  A group is one
+              (image, category).
+  mask IoU    inter = popcount(d & g), union = |d| + |g| - inter, integers; iou = double(inter) / double(union), one IEEE division;
+              0 when union == 0.
+  box IoU     float64, no fused multiply-add:  w = min(dx + dw, gx + gw) - max(dx, gx), h likewise; 0 if w <= 0 or h <= 0; else
+              i = w h, u = (dw dh + gw gh) - i, iou = i / u.
+  thresholds  T = np.linspace(0.5, 0.95, 10) (the ninth is 0.8999999999999999); a pair matches at t when iou >= min(t, 1 - 1e-10).
+  areas       all [0, 1e10], small [0, 32^2], medium [32^2, 96^2], large [96^2, 1e10], both ends inclusive.  The ground-truth area is
+              the visible mask's pixel count (both IoU types), the detection's its mask's pixel count (segm) or w h (bbox).  Within a
+              range a ground truth is ignored when flagged or when its area is outside.
+  matching    per group, threshold and range: the detections stable-sorted by descending score (equal scores keep input order), the
+              first 100 visited in that order.  A detection takes the unmatched ground truth of highest IoU at or above the
+              threshold; of equal IoUs the later in ground-truth order (non-ignored first, each part in input order); an ignored one
+              only when no non-ignored one qualifies.  A detection matched to an ignored ground truth is ignored; so is an unmatched
+              one whose area is outside the range.  A ground truth is matched at most once.  No crowd instances.
+  accumulate  per category, threshold, range and maxDet in {1, 10, 100}: each image's first maxDet detections, concatenated over the
+              images in ascending order, stable-sorted by descending score, the ignored dropped; cumulative tp and fp;
+              recall = tp / n_pos (n_pos the non-ignored ground truths; a category with n_pos == 0 is left out of every mean);
+              precision = tp / (tp + fp + eps), eps = np.spacing(1), made non-increasing from the right, sampled at
+              np.linspace(0, 1, 101) with searchsorted(recall, r, side="left"), 0 beyond the last recall.
+  reported    AP (mean over thresholds, recall levels, categories at all / 100), AP50, AP75, AP_small / medium / large (at 100),
+              AR1 / AR10 / AR100 (the last recall, or 0, at all); a mean over nothing is -1.
+
+``mask_ious``, ``box_ious`` and ``coco_match`` each have a kernel path and a ``_library`` torch statement of the same definition, used
+for CPU tensors, under ``policy.disable_fused`` and -- the matching -- for groups of more than 64 ground truths.
 """
 import math
 
 import numpy as np
 import torch
 
-from . import ops, policy
+from . import _lib, ops, policy
 
 BOP19 = dict(vsd_delta=15.0, vsd_taus=tuple(round(0.05 * k, 2) for k in range(1, 11)), vsd_normalized=True,
              thresholds=tuple(round(0.05 * k, 2) for k in range(1, 11)), mspd_thresholds=tuple(5.0 * k for k in range(1, 11)),
@@ -367,3 +399,386 @@ def read_bop_csv(path):
                 obj=np.array([int(w[2]) for w in rows], np.int64), score=np.array([w[3] for w in rows], np.float32).reshape(n),
                 R=np.array([w[4].split() for w in rows], np.float32).reshape(n, 3, 3),
                 t=np.array([w[5].split() for w in rows], np.float32).reshape(n, 3), time=np.array([float(w[6]) for w in rows], np.float64))
+
+
+# ------------------------------------------------------------------------------------------------------------------- COCO AP
+COCO_THRESHOLDS = np.linspace(0.5, 0.95, 10)                                # float64; the ninth is 0.8999999999999999
+COCO_AREA_RANGES = np.array([[0.0, 1e10], [0.0, 32.0 ** 2], [32.0 ** 2, 96.0 ** 2], [96.0 ** 2, 1e10]])   # all, small, medium, large
+COCO_MAX_DETS = (1, 10, 100)
+COCO_RECALL_LEVELS = np.linspace(0.0, 1.0, 101)
+COCO_MIN_VISIB = 0.1                                                        # a ground truth below this visib_fract is ignored
+
+
+def _coco_kernels(site, t, *names):
+    return policy.guard(site, cuda=t.is_cuda, have=all(ops.have(n) for n in names))
+
+
+def _coco_device(device, *operands):
+    if device is not None:
+        return torch.device(device)
+    for t in operands:
+        if torch.is_tensor(t):
+            return t.device
+    return torch.device("cuda" if torch.cuda.is_available() else "cpu")
+
+
+def _masks_u8(m, dev):
+    t = torch.as_tensor(m).detach()
+    if t.dim() != 3:
+        raise ValueError(f"masks must have shape (N,H,W), got {tuple(t.shape)}")
+    if t.dtype not in (torch.bool, torch.uint8):
+        t = t != 0
+    t = t.to(dev).contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def _pairs_i32(pairs, dev, n_det, n_gt):
+    p = torch.as_tensor(pairs).detach().to(device=dev, dtype=torch.int32).reshape(-1, 2).contiguous()
+    if p.shape[0] and (int(p.min()) < 0 or int(p[:, 0].max()) >= n_det or int(p[:, 1].max()) >= n_gt):
+        raise ValueError(f"pairs must index rows [0, {n_det}) and [0, {n_gt})")
+    return p
+
+
+def _mask_counts_library(dm, gm, pairs, chunk_bytes=1 << 28):
+    """The library statement of the mask counts: dense products, a chunk of pairs at a time."""
+    da, ga = (dm != 0).flatten(1).sum(1).int(), (gm != 0).flatten(1).sum(1).int()
+    hw = max(1, dm.shape[1] * dm.shape[2])
+    step = max(1, chunk_bytes // hw)
+    p = pairs.long()
+    inter = [((dm[p[i:i + step, 0]] != 0) & (gm[p[i:i + step, 1]] != 0)).flatten(1).sum(1).int() for i in range(0, p.shape[0], step)]
+    return (torch.cat(inter) if inter else torch.zeros(0, dtype=torch.int32, device=dm.device)), da, ga
+
+
+def _mask_counts(det_masks, gt_masks, pairs, device=None, site="eval.mask_ious"):
+    dev = _coco_device(device, det_masks, gt_masks)
+    dm, gm = _masks_u8(det_masks, dev), _masks_u8(gt_masks, dev)
+    if tuple(dm.shape[1:]) != tuple(gm.shape[1:]) and dm.shape[0] and gm.shape[0]:
+        raise ValueError(f"detection masks are {tuple(dm.shape[1:])}, ground-truth masks {tuple(gm.shape[1:])}")
+    p = _pairs_i32(pairs, dev, dm.shape[0], gm.shape[0])
+    if dm.shape[1] * dm.shape[2] >= 1 and gm.shape[1] * gm.shape[2] >= 1 and _coco_kernels(site, dm, "mask_pack", "mask_pair_inter"):
+        dp, da = ops.mask_pack(dm)
+        gp, ga = ops.mask_pack(gm)
+        inter = ops.mask_pair_inter(dp, gp, p) if p.shape[0] else torch.zeros(0, dtype=torch.int32, device=dev)
+        return inter, da, ga, p
+    return _mask_counts_library(dm, gm, p) + (p,)
+
+
+def _iou_from_counts(inter, da, ga, p):
+    i = inter.long()
+    u = da.long()[p[:, 0].long()] + ga.long()[p[:, 1].long()] - i
+    return torch.where(u > 0, i.double() / u.clamp(min=1).double(), torch.zeros_like(i, dtype=torch.float64))
+
+
+@torch.no_grad()
+def mask_ious(det_masks, gt_masks, pairs, device=None):
+    """IoU of P (detection, ground truth) mask pairs -> (P,) float64 on the device.  det_masks (Nd,H,W), gt_masks (Ng,H,W) bool or
+    uint8 (non-zero = set), pairs (P,2) rows into them.  inter = popcount(d & g), union = |d| + |g| - inter, integers;
+    iou = double(inter) / double(union), 0 for an empty union.  Kernels on device tensors (``ops.mask_pack``, ``ops.mask_pair_inter``),
+    the dense torch statement (``_mask_counts_library``) on CPU tensors or when ``policy.disable_fused`` names a kernel."""
+    return _iou_from_counts(*_mask_counts(det_masks, gt_masks, pairs, device))
+
+
+def _box_ious_library(db, gb, pairs):
+    """The library statement of the box IoU: float64 tensor operations, one rounding each."""
+    d, g = db[pairs[:, 0].long()], gb[pairs[:, 1].long()]
+    w = torch.minimum(d[:, 0] + d[:, 2], g[:, 0] + g[:, 2]) - torch.maximum(d[:, 0], g[:, 0])
+    h = torch.minimum(d[:, 1] + d[:, 3], g[:, 1] + g[:, 3]) - torch.maximum(d[:, 1], g[:, 1])
+    ok = (w > 0) & (h > 0)
+    i = w * h
+    da, ga = d[:, 2] * d[:, 3], g[:, 2] * g[:, 3]
+    u = (da + ga) - i
+    return torch.where(ok, i / torch.where(ok, u, torch.ones_like(u)), torch.zeros_like(i))
+
+
+@torch.no_grad()
+def box_ious(det_boxes, gt_boxes, pairs, device=None):
+    """IoU of P box pairs -> (P,) float64.  Boxes (n,4) = x y w h, float64 (other types are converted):
+    w = min(dx + dw, gx + gw) - max(dx, gx), h likewise; 0 when w <= 0 or h <= 0; else i = w h, u = (dw dh + gw gh) - i, i / u, no
+    fused multiply-add.  ``ops.box_pair_iou`` on device tensors, ``_box_ious_library`` otherwise."""
+    dev = _coco_device(device, det_boxes, gt_boxes)
+    db = torch.as_tensor(det_boxes).detach().to(device=dev, dtype=torch.float64).reshape(-1, 4).contiguous()
+    gb = torch.as_tensor(gt_boxes).detach().to(device=dev, dtype=torch.float64).reshape(-1, 4).contiguous()
+    p = _pairs_i32(pairs, dev, db.shape[0], gb.shape[0])
+    if p.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.float64, device=dev)
+    if _coco_kernels("eval.box_ious", db, "box_pair_iou"):
+        return ops.box_pair_iou(db, gb, p)
+    return _box_ious_library(db, gb, p)
+
+
+def _coco_match_library(ious, iou_off, groups, det_area, gt_area, gt_ignore, thresholds, area_ranges, rows=None, cells=1 << 24):
+    """The library statement of the matching: the groups side by side, padded to the largest, one step per detection rank.
+    rows: the groups to match (default all); the detections of the others stay at -1 / 0."""
+    dev = ious.device
+    NT, NA = thresholds.shape[0], area_ranges.shape[0]
+    match = torch.full((det_area.shape[0], NT, NA), -1, dtype=torch.int32, device=dev)
+    ignore = torch.zeros(det_area.shape[0], NT, NA, dtype=torch.uint8, device=dev)
+    grp = groups.long() if rows is None else groups.long()[rows]
+    off = iou_off if rows is None else iou_off[rows]
+    if grp.shape[0] == 0:
+        return match, ignore
+    bar0 = torch.minimum(thresholds, torch.full_like(thresholds, 1.0 - 1e-10))[None, :, None, None]
+    lo, hi = area_ranges[:, 0], area_ranges[:, 1]
+    Dm, Gm = int(grp[:, 1].max()), max(1, int(grp[:, 3].max()))              # (a padded column, never open, when no group has a ground truth)
+    step = max(1, cells // max(1, NT * NA * max(Gm, 1)))
+    for s in range(0, grp.shape[0], step):
+        g4, o = grp[s:s + step], off[s:s + step]
+        n = g4.shape[0]
+        gi = torch.arange(Gm, device=dev)[None]
+        gok = gi < g4[:, 3, None]                                                                  # (n,Gm)
+        gsel = (g4[:, 2, None] + gi).clamp(max=max(gt_area.shape[0] - 1, 0))
+        if gt_area.shape[0]:
+            ga, gf = gt_area[gsel], gt_ignore[gsel] != 0
+        else:
+            ga, gf = torch.zeros(n, Gm, dtype=torch.float64, device=dev), torch.zeros(n, Gm, dtype=torch.bool, device=dev)
+        ign = gf[:, None] | (ga[:, None] < lo[None, :, None]) | (ga[:, None] > hi[None, :, None])   # (n,NA,Gm)
+        ign = ign[:, None].expand(n, NT, NA, Gm)
+        taken = (~gok)[:, None, None].expand(n, NT, NA, Gm).clone()
+        for d in range(Dm):
+            live = d < g4[:, 1]                                                                    # (n,)
+            isel = (o[:, None] + d * g4[:, 3, None] + gi).clamp(min=0, max=max(ious.shape[0] - 1, 0))
+            v = ious[isel] if ious.shape[0] else torch.zeros(n, Gm, dtype=torch.float64, device=dev)
+            v = v[:, None, None].expand(n, NT, NA, Gm)
+            cand = ~taken & (v >= bar0) & live[:, None, None, None]
+            m = torch.full((n, NT, NA), -1, dtype=torch.long, device=dev)
+            for part in (cand & ~ign, cand & ign):
+                w = torch.where(part, v, torch.full_like(v, -1.0))
+                best = w.max(3, keepdim=True)[0]
+                last = torch.where(part & (w == best), gi[0].expand_as(w), torch.full_like(w, -1, dtype=torch.long)).max(3)[0]
+                m = torch.where(m >= 0, m, last)                                                   # the ignored part only when nothing matched
+            hit = m >= 0
+            mc = m.clamp(min=0)
+            taken = taken | (hit[..., None] & (gi[0] == mc[..., None]))
+            da = det_area[(g4[:, 0] + d).clamp(max=max(det_area.shape[0] - 1, 0))]
+            outside = (da[:, None] < lo[None]) | (da[:, None] > hi[None])                           # (n,NA)
+            ig = torch.where(hit, torch.gather(ign, 3, mc[..., None])[..., 0], outside[:, None].expand(n, NT, NA))
+            r = (g4[:, 0] + d)[live]
+            match[r] = m[live].int()
+            ignore[r] = ig[live].to(torch.uint8)
+    return match, ignore
+
+
+@torch.no_grad()
+def coco_match(ious, iou_off, groups, det_area, gt_area, gt_ignore, thresholds=COCO_THRESHOLDS, area_ranges=COCO_AREA_RANGES, device=None):
+    """The greedy matching of every group = (image, category) at every threshold and area range.
+
+    groups (n,4) = first detection, detections D, first ground truth, ground truths G of the group; the group's detections are
+    det rows [first, first + D) ALREADY in visiting order (descending score, truncated to 100); iou_off (n,): ious[iou_off + d G + g]
+    is the IoU of the group's detection d and ground truth g; det_area (Dn,), gt_area (Gn,) float64; gt_ignore (Gn,).
+    -> (match (Dn,NT,NA) int32, the index of the matched ground truth inside its group or -1; ignore (Dn,NT,NA) uint8).
+    Per threshold t and range [lo, hi]: a ground truth is ignored when flagged or its area is outside the range; a detection takes
+    the unmatched ground truth of highest IoU >= min(t, 1 - 1e-10) among the non-ignored ones (of equal IoUs the later in input
+    order), and only when there is none the same among the ignored ones; it is ignored when its match is, or when it has no match
+    and its own area is outside the range.  ``ops.coco_match`` (one workgroup per group, 64-bit matched mask) serves groups of at most
+    64 ground truths on device tensors; LARGER GROUPS, CPU tensors and ``policy.disable_fused`` go to ``_coco_match_library``, the same
+    definition in torch statements."""
+    dev = _coco_device(device, ious)
+    f64 = lambda a: torch.as_tensor(a).detach().to(device=dev, dtype=torch.float64).contiguous()
+    v, da, ga, th, ar = f64(ious).reshape(-1), f64(det_area).reshape(-1), f64(gt_area).reshape(-1), f64(thresholds).reshape(-1), f64(area_ranges).reshape(-1, 2)
+    gr = torch.as_tensor(groups).detach().to(device=dev, dtype=torch.int32).reshape(-1, 4).contiguous()
+    off = torch.as_tensor(iou_off).detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    gf = (torch.as_tensor(gt_ignore).detach().to(dev) != 0).to(torch.uint8).reshape(-1).contiguous()
+    if off.shape[0] != gr.shape[0] or gf.shape[0] != ga.shape[0]:
+        raise ValueError(f"coco_match: {gr.shape[0]} groups but {off.shape[0]} offsets; {ga.shape[0]} areas but {gf.shape[0]} ignore flags")
+    if gr.shape[0]:
+        g = gr.long()
+        if bool((g < 0).any() | (off < 0).any() | (g[:, 0] + g[:, 1] > da.shape[0]).any() | (g[:, 2] + g[:, 3] > ga.shape[0]).any() |
+                (off + g[:, 1] * g[:, 3] > v.shape[0]).any()):
+            raise ValueError("coco_match: a group lies outside the detection, ground-truth or IoU arrays")
+    if gr.shape[0] and da.shape[0] and _coco_kernels("eval.coco_match", v, "coco_match"):
+        small = gr[:, 3] <= _lib.header_constant("S6D_COCO_MATCH_MAX_GT")
+        if bool(small.all()):
+            return ops.coco_match(v, off, gr, da, ga, gf, th, ar)
+        big = torch.nonzero(~small)[:, 0]
+        keep = torch.nonzero(small)[:, 0]
+        m, i = ops.coco_match(v, off[keep].contiguous(), gr[keep].contiguous(), da, ga, gf, th, ar)
+        ml, il = _coco_match_library(v, off, gr, da, ga, gf, th, ar, rows=big)
+        mine = torch.zeros(da.shape[0], dtype=torch.bool, device=dev)
+        for r in gr[big].long().tolist():
+            mine[r[0]:r[0] + r[1]] = True
+        return torch.where(mine[:, None, None], ml, m), torch.where(mine[:, None, None], il, i)
+    return _coco_match_library(v, off, gr, da, ga, gf, th, ar)
+
+
+def detections_from_records(records):
+    """The records of a BOP result file (``handoff.detection_records`` / ``read_bop_json``) -> the ``detections`` of ``coco_scores``:
+    im (n,2) = (scene_id, image_id), category, score, bbox (n,4) x y w h float64, masks (n,H,W) bool (when every record has one)."""
+    from .ism import handoff
+    n = len(records)
+    out = dict(im=np.array([[int(r["scene_id"]), int(r["image_id"])] for r in records], np.int64).reshape(n, 2),
+               category=np.array([int(r["category_id"]) for r in records], np.int64),
+               score=np.array([float(r["score"]) for r in records], np.float64),
+               bbox=np.array([r["bbox"] for r in records], np.float64).reshape(n, 4))
+    if n and all(r.get("segmentation") is not None for r in records):
+        for r in records:
+            if isinstance(r["segmentation"].get("counts"), (str, bytes)):
+                raise ValueError("the segmentation of a record is a COMPRESSED RLE string: only uncompressed run-length lists "
+                                 "(what save_json_bop23 writes) are read")
+        out["masks"] = np.stack([handoff.rle_to_mask(r["segmentation"]) for r in records])
+    return out
+
+
+def detections_from_handoff(frames, dataset_name="ycbv"):
+    """A batch of ``handoff.Detections`` (one per frame) -> the ``detections`` of ``coco_scores``, the masks staying dense tensors on
+    their device (no RLE round trip); categories and boxes as ``handoff.detection_records`` writes them."""
+    from .ism import handoff
+    frames = [frames] if isinstance(frames, handoff.Detections) else list(frames)
+    im, cat, score, box, masks = [], [], [], [], []
+    for f in frames:
+        obj = f.object_ids.cpu().numpy()
+        b = f.boxes.detach().cpu().double().numpy().reshape(-1, 4)
+        im.append(np.tile(np.array([[int(f.scene_id), int(f.image_id)]], np.int64), (len(obj), 1)))
+        cat.append(handoff.LMO_OBJECT_IDS[obj] if dataset_name == "lmo" else obj + 1)
+        score.append(f.scores.detach().cpu().double().numpy())
+        box.append(np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1))
+        masks.append(f.masks)
+    return dict(im=np.concatenate(im), category=np.concatenate(cat).astype(np.int64), score=np.concatenate(score),
+                bbox=np.concatenate(box), masks=torch.cat(masks))
+
+
+def _as_detections(detections):
+    from .ism import handoff
+    if isinstance(detections, dict):
+        return detections
+    if isinstance(detections, handoff.Detections) or (len(detections) and isinstance(detections[0], handoff.Detections)):
+        return detections_from_handoff(detections)
+    return detections_from_records(list(detections))
+
+
+def _mean(a):
+    return float(np.mean(np.ascontiguousarray(a).reshape(-1))) if np.size(a) else -1.0          # one flat sum, in (threshold, recall, category) order
+
+
+@torch.no_grad()
+def coco_scores(detections, ground_truths, iou_type="segm", device=None):
+    """COCO AP / AR of detections against ground truths, by the DEFINITION below (``iou_type`` "segm": mask IoU, "bbox": box IoU).
+
+    detections: dict(im, category, score, masks (D,H,W) | bbox (D,4) x y w h) -- the masks may be dense device tensors --, or a
+    batch of ``handoff.Detections``, or the records of a result file (``read_bop_json``).  ground_truths: dict(im, category,
+    masks (G,H,W) visible masks, bbox (G,4) visible boxes (bbox only), ignore (G,), optionally area (G,) instead of masks for
+    bbox).  ``im`` is (n,) or (n,k) integers (k = 2: scene, image); a group is one (im, category).
+    -> dict(AP, AP50, AP75, AP_small, AP_medium, AP_large, AR1, AR10, AR100, detections, ground_truths, ignored, groups).
+
+    Definition.  Thresholds T = linspace(0.5, 0.95, 10); area ranges all [0, 1e10], small [0, 32^2], medium [32^2, 96^2], large
+    [96^2, 1e10], both ends inclusive; the ground-truth area is the visible mask's pixel count (both IoU types), the detection's its
+    mask's pixel count (segm) or w h (bbox).  Per group the detections are stable-sorted by descending score, the first 100 kept and
+    matched as ``coco_match`` states, with the IoUs of ``mask_ious`` / ``box_ious``.  Per category, threshold, range and
+    maxDet in {1, 10, 100}: each image's first maxDet detections, concatenated over the images in ascending ``im`` order, are
+    stable-sorted by descending score and the ignored ones dropped; tp / fp are cumulative; recall = tp / n_pos (n_pos = the
+    category's non-ignored ground truths in the range; a category with n_pos = 0 is left out of every mean), precision =
+    tp / (tp + fp + eps) with eps = np.spacing(1), made non-increasing from the right and sampled at the recall levels
+    linspace(0, 1, 101) with searchsorted(recall, r, side="left"), 0 beyond the last recall.  AP = the mean over thresholds, recall
+    levels and categories at (all, 100); AP50, AP75 at one threshold; AP_small / medium / large at 100; AR1 / 10 / 100 = the mean of
+    the last recall (0 without detections) at all; a mean over nothing is -1.  There are no crowd instances.
+    Grouping, the sorts, the cumulative sums and the sampling are host code in float64; the IoUs and the matching run on
+    ``device`` (kernels on a GPU, the library statements on the CPU)."""
+    if iou_type not in ("segm", "bbox"):
+        raise ValueError(f"iou_type must be 'segm' or 'bbox', got {iou_type!r}")
+    det, gt = _as_detections(detections), ground_truths
+    dev = _coco_device(device, det.get("masks") if iou_type == "segm" else None)
+    key = lambda x, n: np.asarray(torch.as_tensor(x).cpu() if torch.is_tensor(x) else x, np.int64).reshape(n, -1)
+    d_score = np.asarray(torch.as_tensor(det["score"]).cpu() if torch.is_tensor(det["score"]) else det["score"], np.float64).reshape(-1)
+    D, G = d_score.shape[0], np.asarray(gt["category"]).reshape(-1).shape[0]
+    d_key = np.concatenate([key(det["im"], D), key(det["category"], D)], 1) if D else None
+    g_key = np.concatenate([key(gt["im"], G), key(gt["category"], G)], 1) if G else None
+    if D and G and d_key.shape[1] != g_key.shape[1]:
+        raise ValueError("detections and ground truths name their images differently")
+    both = np.concatenate([d_key, g_key]) if D and G else (d_key if D else g_key if G else np.zeros((0, 2), np.int64))
+    uniq, inv = np.unique(both, axis=0, return_inverse=True) if both.shape[0] else (both, np.zeros(0, np.int64))
+    inv = np.asarray(inv).reshape(-1)
+    NG = uniq.shape[0]
+    d_grp, g_grp = (inv[:D], inv[D:]) if D and G else ((inv, inv[:0]) if D else (inv[:0], inv))
+    g_ign = np.asarray(gt.get("ignore", np.zeros(G, bool))).astype(bool).reshape(-1)
+    # visiting order of the detections: by group, then descending score (stable), the first 100 of a group
+    order = np.lexsort((-d_score, d_grp)) if D else np.zeros(0, np.int64)
+    first = np.searchsorted(d_grp[order], np.arange(NG), side="left")
+    rank = np.arange(D) - first[d_grp[order]] if D else np.zeros(0, np.int64)
+    kd = order[rank < COCO_MAX_DETS[-1]]
+    k_grp, k_rank = d_grp[kd], rank[rank < COCO_MAX_DETS[-1]]
+    go = np.argsort(g_grp, kind="stable")
+    Dg, Gg = np.bincount(k_grp, minlength=NG).astype(np.int64), np.bincount(g_grp, minlength=NG).astype(np.int64)
+    d_off, g_off = np.cumsum(Dg) - Dg, np.cumsum(Gg) - Gg
+    i_off = np.cumsum(Dg * Gg) - Dg * Gg
+    # every (detection, ground truth) pair of every group, detection-major: the rows of the IoU blocks
+    per_det = Gg[k_grp]
+    p_det = np.repeat(np.arange(len(kd)), per_det)
+    p_gt = g_off[k_grp[p_det]] + (np.arange(len(p_det)) - np.repeat(np.cumsum(per_det) - per_det, per_det))
+    pairs = np.stack([kd[p_det], go[p_gt]], 1).astype(np.int32) if len(p_det) else np.zeros((0, 2), np.int32)
+    if iou_type == "segm":
+        if D and G:
+            inter, da, ga, p = _mask_counts(det["masks"], gt["masks"], pairs, dev, site="eval.coco_scores")
+            iou = _iou_from_counts(inter, da, ga, p)
+            d_area, g_area = da.double(), ga.double()
+        else:
+            iou = torch.zeros(0, dtype=torch.float64, device=dev)
+            d_area = _masks_u8(det["masks"], dev).flatten(1).ne(0).sum(1).double() if D else torch.zeros(0, dtype=torch.float64, device=dev)
+            g_area = _masks_u8(gt["masks"], dev).flatten(1).ne(0).sum(1).double() if G else torch.zeros(0, dtype=torch.float64, device=dev)
+    else:
+        db = torch.as_tensor(det["bbox"]).detach().to(device=dev, dtype=torch.float64).reshape(-1, 4)
+        iou = box_ious(db, gt["bbox"], pairs, dev) if D and G else torch.zeros(0, dtype=torch.float64, device=dev)
+        d_area = db[:, 2] * db[:, 3]
+        if gt.get("area") is not None:
+            g_area = torch.as_tensor(gt["area"]).detach().to(device=dev, dtype=torch.float64).reshape(-1)
+        else:
+            g_area = _masks_u8(gt["masks"], dev).flatten(1).ne(0).sum(1).double() if G else torch.zeros(0, dtype=torch.float64, device=dev)
+    idx = lambda a: torch.as_tensor(a, device=dev)
+    k_area, s_area = d_area[idx(kd)] if len(kd) else d_area[:0], g_area[idx(go)] if G else g_area[:0]
+    s_ign = g_ign[go]
+    table = np.stack([d_off, Dg, g_off, Gg], 1).astype(np.int32)
+    if len(kd):
+        match, dig = coco_match(iou, i_off, table, k_area, s_area, s_ign.astype(np.uint8), COCO_THRESHOLDS, COCO_AREA_RANGES, dev)
+        match, dig = match.cpu().numpy() >= 0, dig.cpu().numpy() != 0                               # (Dk,NT,NA)
+    else:
+        match = dig = np.zeros((0, len(COCO_THRESHOLDS), len(COCO_AREA_RANGES)), bool)
+    # accumulation: host code in float64
+    ga_h, k_score = s_area.cpu().numpy(), d_score[kd]
+    cat_col = uniq.shape[1] - 1
+    g_cat, k_cat = (uniq[g_grp[go], cat_col] if G else np.zeros(0, np.int64)), (uniq[k_grp, cat_col] if len(kd) else np.zeros(0, np.int64))
+    cats = np.unique(uniq[:, cat_col]) if NG else np.zeros(0, np.int64)
+    NT, NA, NM, NR = len(COCO_THRESHOLDS), len(COCO_AREA_RANGES), len(COCO_MAX_DETS), len(COCO_RECALL_LEVELS)
+    precision, recall = -np.ones((NT, NR, len(cats), NA, NM)), -np.ones((NT, len(cats), NA, NM))
+    eps = np.spacing(1)
+    for ki, c in enumerate(cats):
+        gsel = g_cat == c
+        for ai, (lo, hi) in enumerate(COCO_AREA_RANGES):
+            n_pos = int(np.count_nonzero(~(s_ign[gsel] | (ga_h[gsel] < lo) | (ga_h[gsel] > hi))))
+            if n_pos == 0:
+                continue
+            for mi, md in enumerate(COCO_MAX_DETS):
+                sel = np.nonzero((k_cat == c) & (k_rank < md))[0]                                   # by image, then by rank
+                sel = sel[np.argsort(-k_score[sel], kind="stable")]
+                for ti in range(NT):
+                    use = ~dig[sel, ti, ai]
+                    hit = match[sel, ti, ai][use]
+                    tp, fp = np.cumsum(hit).astype(np.float64), np.cumsum(~hit).astype(np.float64)
+                    nd = len(tp)
+                    rc, pr = tp / n_pos, tp / (fp + tp + eps)
+                    recall[ti, ki, ai, mi] = rc[-1] if nd else 0.0
+                    pr = np.maximum.accumulate(pr[::-1])[::-1]                                     # non-increasing from the right
+                    at = np.searchsorted(rc, COCO_RECALL_LEVELS, side="left")
+                    q = np.zeros(NR)
+                    q[at < nd] = pr[at[at < nd]]
+                    precision[ti, :, ki, ai, mi] = q
+    live = recall[0] > -1                                                                          # (K,NA,NM): n_pos > 0
+    ap = lambda ts, ai: _mean(precision[ts][:, :, live[:, ai, NM - 1], ai, NM - 1])
+    ar = lambda mi: _mean(recall[:, live[:, 0, mi], 0, mi])
+    every = slice(None)
+    return {"AP": ap(every, 0), "AP50": ap(slice(0, 1), 0), "AP75": ap(slice(5, 6), 0), "AP_small": ap(every, 1), "AP_medium": ap(every, 2),
+            "AP_large": ap(every, 3), "AR1": ar(0), "AR10": ar(1), "AR100": ar(2), "iou_type": iou_type, "detections": int(D),
+            "ground_truths": int(G), "ignored": int(g_ign.sum()), "groups": int(NG)}
+
+
+def read_bop_json(path):
+    """The records ``ism.handoff.save_json_bop23`` writes (a JSON list of scene_id, image_id, category_id, bbox x y w h, score, time,
+    segmentation = {"counts": run lengths in column-major order, "size": [H, W]}) -> dict(scene, im, category (n,) int64,
+    score (n,) float64, bbox (n,4) float64, time (n,) float64, masks (n,H,W) bool or None when the records carry none), the masks
+    decoded through ``handoff.rle_to_mask``.  A ``counts`` that is a compressed RLE STRING is refused: only the uncompressed lists are
+    read."""
+    import json
+    with open(path) as f:
+        records = json.load(f)
+    if not isinstance(records, list):
+        raise ValueError(f"{path}: a JSON list of detection records expected")
+    d = detections_from_records(records)
+    return dict(scene=d["im"][:, 0].copy(), im=d["im"][:, 1].copy(), category=d["category"], score=d["score"], bbox=d["bbox"],
+                time=np.array([float(r.get("time", -1.0)) for r in records], np.float64), masks=d.get("masks"))

@@ -825,6 +825,97 @@ def vsd_counts(depth_est, depth_gt, depth_test, test_index, cams, delta, taus, s
     return union, inter, ge
 
 
+# ------------------------------------------------------------------ COCO AP of ISM results (csrc/s6d_cocoeval.hip)
+def _pairs(pairs, n_det, n_gt, what):
+    _chk(pairs, torch.int32, "pairs", 2)
+    if pairs.shape[1] != 2:
+        raise ValueError(f"{what}: pairs (P,2) expected, got {tuple(pairs.shape)}")
+    if pairs.shape[0] and (int(pairs.min()) < 0 or int(pairs[:, 0].max()) >= n_det or int(pairs[:, 1].max()) >= n_gt):
+        raise ValueError(f"{what}: pairs must index rows [0, {n_det}) and [0, {n_gt})")
+    return pairs.shape[0]
+
+
+def mask_pack(masks):
+    """masks (N,H,W) uint8 or bool -> (packed (N, ceil(H W / 64)) int64, area (N,) int32): bit k of word j is pixel 64 j + k in
+    row-major order, the bits past H W are zero (include/sam6d_hip.h: s6d_mask_pack_u8)."""
+    if masks.dtype == torch.bool and masks.is_cuda and masks.is_contiguous():
+        masks = masks.view(torch.uint8)
+    _chk(masks, torch.uint8, "masks", 3)
+    N, H, W = masks.shape
+    if H * W < 1:
+        raise ValueError(f"mask_pack: masks (N,H,W) with H W >= 1 expected, got {tuple(masks.shape)}")
+    packed = torch.empty(N, (H * W + 63) // 64, dtype=torch.int64, device=masks.device)
+    area = torch.empty(N, dtype=torch.int32, device=masks.device)
+    _call("s6d_mask_pack_u8", _ptr(masks), N, H * W, _ptr(packed), _ptr(area), _stream())
+    return packed, area
+
+
+def mask_pair_inter(det_packed, gt_packed, pairs):
+    """det_packed (Nd,words), gt_packed (Ng,words) int64 (``mask_pack``), pairs (P,2) int32 = (detection row, ground-truth row) ->
+    (P,) int32 popcount(d & g).  A pair has the same count whatever else is in the list (include/sam6d_hip.h: s6d_mask_pair_inter).
+    Rows outside the arrays are refused here, on the host."""
+    _chk(det_packed, torch.int64, "det_packed", 2)
+    _chk(gt_packed, torch.int64, "gt_packed", 2)
+    if det_packed.shape[1] != gt_packed.shape[1] or det_packed.shape[1] < 1:
+        raise ValueError(f"mask_pair_inter: det_packed (Nd,words), gt_packed (Ng,words) expected, got {tuple(det_packed.shape)}, "
+                         f"{tuple(gt_packed.shape)}")
+    P = _pairs(pairs, det_packed.shape[0], gt_packed.shape[0], "mask_pair_inter")
+    inter = torch.empty(P, dtype=torch.int32, device=pairs.device)
+    _call("s6d_mask_pair_inter", _ptr(det_packed), det_packed.shape[0], _ptr(gt_packed), gt_packed.shape[0], det_packed.shape[1],
+          _ptr(pairs), P, _ptr(inter), _stream())
+    return inter
+
+
+def box_pair_iou(det_boxes, gt_boxes, pairs):
+    """det_boxes (Nd,4), gt_boxes (Ng,4) float64 = x y w h, pairs (P,2) int32 -> (P,) float64 IoU in the stated operation order
+    (include/sam6d_hip.h: s6d_box_pair_iou_f64)."""
+    _chk(det_boxes, torch.float64, "det_boxes", 2)
+    _chk(gt_boxes, torch.float64, "gt_boxes", 2)
+    if det_boxes.shape[1] != 4 or gt_boxes.shape[1] != 4:
+        raise ValueError(f"box_pair_iou: det_boxes (Nd,4), gt_boxes (Ng,4) expected, got {tuple(det_boxes.shape)}, {tuple(gt_boxes.shape)}")
+    P = _pairs(pairs, det_boxes.shape[0], gt_boxes.shape[0], "box_pair_iou")
+    iou = torch.empty(P, dtype=torch.float64, device=pairs.device)
+    _call("s6d_box_pair_iou_f64", _ptr(det_boxes), det_boxes.shape[0], _ptr(gt_boxes), gt_boxes.shape[0], _ptr(pairs), P, _ptr(iou),
+          _stream())
+    return iou
+
+
+def coco_match(ious, iou_off, groups, det_area, gt_area, gt_ignore, thresholds, area_ranges):
+    """Greedy matching of every group = (image, category).  groups (n,4) int32 = first detection, detections, first ground truth,
+    ground truths (at most S6D_COCO_MATCH_MAX_GT = 64); iou_off (n,) int64: where the group's (D,G) row-major block of ``ious``
+    (float64) begins; det_area (Dn,), gt_area (Gn,) float64; gt_ignore (Gn,) uint8; thresholds (NT,), area_ranges (NA,2) float64,
+    NT NA <= 64 -> (match (Dn,NT,NA) int32: the ground truth's index inside its group or -1, ignore (Dn,NT,NA) uint8)
+    (include/sam6d_hip.h: s6d_coco_match).  The group table is checked here, on the host."""
+    _chk(ious, torch.float64, "ious", 1)
+    _chk(iou_off, torch.int64, "iou_off", 1)
+    _chk(groups, torch.int32, "groups", 2)
+    _chk(det_area, torch.float64, "det_area", 1)
+    _chk(gt_area, torch.float64, "gt_area", 1)
+    _chk(gt_ignore, torch.uint8, "gt_ignore", 1)
+    _chk(thresholds, torch.float64, "thresholds", 1)
+    _chk(area_ranges, torch.float64, "area_ranges", 2)
+    n, NT, NA, Dn, Gn = groups.shape[0], thresholds.shape[0], area_ranges.shape[0], det_area.shape[0], gt_area.shape[0]
+    if groups.shape[1] != 4 or tuple(iou_off.shape) != (n,) or tuple(gt_ignore.shape) != (Gn,) or area_ranges.shape[1] != 2 or \
+            NT < 1 or NA < 1 or NT * NA > 64:
+        raise ValueError(f"coco_match: groups (n,4), iou_off (n,), gt_area and gt_ignore (Gn,), thresholds (NT,), area_ranges (NA,2) with "
+                         f"NT NA <= 64 expected, got {tuple(groups.shape)}, {tuple(iou_off.shape)}, {tuple(gt_area.shape)}, "
+                         f"{tuple(gt_ignore.shape)}, {tuple(thresholds.shape)}, {tuple(area_ranges.shape)}")
+    if n:
+        g, o = groups.long(), iou_off
+        bad = (g < 0).any() | (o < 0).any() | (g[:, 0] + g[:, 1] > Dn).any() | (g[:, 2] + g[:, 3] > Gn).any() | \
+            (o + g[:, 1] * g[:, 3] > ious.shape[0]).any()
+        if bool(bad):
+            raise ValueError("coco_match: a group lies outside the detection, ground-truth or IoU arrays")
+        if int(g[:, 3].max()) > _lib.header_constant("S6D_COCO_MATCH_MAX_GT"):
+            raise ValueError(f"coco_match: a group has {int(g[:, 3].max())} ground truths, more than S6D_COCO_MATCH_MAX_GT")
+    params = torch.cat([thresholds, area_ranges.reshape(-1)]).contiguous()
+    match = torch.full((Dn, NT, NA), -1, dtype=torch.int32, device=groups.device)
+    ignore = torch.zeros(Dn, NT, NA, dtype=torch.uint8, device=groups.device)
+    _call("s6d_coco_match", _ptr(ious), _ptr(iou_off), _ptr(groups), _ptr(det_area), _ptr(gt_area), _ptr(gt_ignore), _ptr(params), n,
+          NT, NA, Dn, Gn, ious.shape[0], _ptr(match), _ptr(ignore), _stream())
+    return match, ignore
+
+
 def upsample_gather(up, choose, H, W, C):
     """up (B,196,16*C) f32, choose (B,n) int64 -> (B,n,C): bilinear x4 of the pixel-shuffled map at chosen pixels."""
     _chk(up, torch.float32, "up", 3)
@@ -1568,7 +1659,8 @@ def have(name):
                "linear_attn_focus": "s6d_linear_attn_focus_f32", "linear_attention": "s6d_linear_attention_f32", "project_bbox": "s6d_project_bbox_frames_f32",
                "template_boxes": "s6d_template_boxes_u8", "template_points": "s6d_template_points_f32", "template_pem_crops": "s6d_template_pem_crops_f32",
                "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32",
-               "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32"}.get(name)
+               "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32",
+               "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):

@@ -25,16 +25,11 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
-def load_dataset(root, split, scenes, min_visib=0.1):
-    """-> (models {obj: dict}, ground_truths dict, images dict, index {(scene, im): image number})."""
-    from PIL import Image
-
-    from sam6d_amd import render
+def walk_scenes(root, split, scenes):
+    """The scene walk the evaluation tools share (tools/coco_eval.py too): for every scene of ``scenes`` in ascending order and every
+    image its scene_gt.json names, in ascending order, yields (scene, im, scene directory, the image's ground-truth records, their
+    scene_gt_info.json records or None when the file is absent, the image's scene_camera.json record)."""
     base = os.path.join(root, split) if os.path.isdir(os.path.join(root, split)) else root
-    with open(os.path.join(root, "models_eval", "models_info.json")) as f:
-        info = {int(k): v for k, v in json.load(f).items()}
-    index, cams, depths = {}, [], []
-    gt = dict(im=[], obj=[], pose=[])
     for scene in sorted(scenes):
         d = os.path.join(base, f"{scene:06d}")
         with open(os.path.join(d, "scene_gt.json")) as f:
@@ -46,20 +41,33 @@ def load_dataset(root, split, scenes, min_visib=0.1):
             with open(os.path.join(d, "scene_gt_info.json")) as f:
                 gt_info = {int(k): v for k, v in json.load(f).items()}
         for im in sorted(scene_gt):
-            K = np.asarray(scene_cam[im]["cam_K"], np.float64).reshape(3, 3)
-            depth = np.asarray(Image.open(os.path.join(d, "depth", f"{im:06d}.png")), np.float32) * np.float32(scene_cam[im].get("depth_scale", 1.0))
-            index[(scene, im)] = len(cams)
-            cams.append([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
-            depths.append(depth)
-            for j, g in enumerate(scene_gt[im]):
-                if gt_info is not None and float(gt_info[im][j].get("visib_fract", 1.0)) < min_visib:
-                    continue
-                P = np.eye(4)
-                P[:3, :3] = np.asarray(g["cam_R_m2c"], np.float64).reshape(3, 3)
-                P[:3, 3] = np.asarray(g["cam_t_m2c"], np.float64).reshape(3)
-                gt["im"].append(index[(scene, im)])
-                gt["obj"].append(int(g["obj_id"]))
-                gt["pose"].append(P)
+            yield scene, im, d, scene_gt[im], None if gt_info is None else gt_info[im], scene_cam[im]
+
+
+def load_dataset(root, split, scenes, min_visib=0.1):
+    """-> (models {obj: dict}, ground_truths dict, images dict, index {(scene, im): image number})."""
+    from PIL import Image
+
+    from sam6d_amd import render
+    with open(os.path.join(root, "models_eval", "models_info.json")) as f:
+        info = {int(k): v for k, v in json.load(f).items()}
+    index, cams, depths = {}, [], []
+    gt = dict(im=[], obj=[], pose=[])
+    for scene, im, d, records, gt_info, cam in walk_scenes(root, split, scenes):
+        K = np.asarray(cam["cam_K"], np.float64).reshape(3, 3)
+        depth = np.asarray(Image.open(os.path.join(d, "depth", f"{im:06d}.png")), np.float32) * np.float32(cam.get("depth_scale", 1.0))
+        index[(scene, im)] = len(cams)
+        cams.append([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+        depths.append(depth)
+        for j, g in enumerate(records):
+            if gt_info is not None and float(gt_info[j].get("visib_fract", 1.0)) < min_visib:
+                continue
+            P = np.eye(4)
+            P[:3, :3] = np.asarray(g["cam_R_m2c"], np.float64).reshape(3, 3)
+            P[:3, 3] = np.asarray(g["cam_t_m2c"], np.float64).reshape(3)
+            gt["im"].append(index[(scene, im)])
+            gt["obj"].append(int(g["obj_id"]))
+            gt["pose"].append(P)
     if len({d.shape for d in depths}) > 1:
         raise ValueError(f"depth images of different sizes: {sorted({d.shape for d in depths})}")
     models = {}
