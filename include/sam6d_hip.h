@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 131
+#define S6D_ABI_VERSION 132
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -203,6 +203,28 @@ int s6d_raster_views_f32(const float *vertices, const int32_t *faces, const unsi
                          void *workspace, unsigned char *rgb, unsigned char *mask, float *xyz, float *depth, int32_t *face,
                          int32_t *skipped, void *stream);
 long s6d_raster_workspace_bytes(int T, int F, int H, int W);   /* -1 for sizes the entry point refuses */
+
+/* The mip pyramid of an RGB texture, built once per object.  image (Ht,Wt,3) u8, row 0 at the top, 1 <= Ht, Wt <= 8192 (S6D_EINVAL
+ * otherwise) -> pyramid: s6d_texture_pyramid_bytes(Ht, Wt) bytes, 4-byte aligned, one 32-bit word per texel (r | g << 8 | b << 16),
+ * levels 0 .. Lmax = floor(log2(max(Wt, Ht))) one after another, each row-major.  Level 0 is the image; level l + 1 has
+ * max(1, W_l >> 1) x max(1, H_l >> 1) texels, each per channel (a + b + c + d + 2) >> 2 over the columns min(2i, W_l - 1),
+ * min(2i + 1, W_l - 1) and the two rows formed the same way: integers, a box filter.  One kernel, one launch per level. */
+int s6d_texture_pyramid_u8(const unsigned char *image, int Ht, int Wt, void *pyramid, void *stream);
+long s6d_texture_pyramid_bytes(int Ht, int Wt);   /* -1 for sizes the entry point refuses */
+
+/* s6d_raster_views_f32 with a texture in place of the vertex colours: uv (F,3,2) f32, a (u, v) per face CORNER (a seam needs no
+ * duplicated vertices), v upwards as in PLY and OBJ files; pyramid, Ht, Wt: what s6d_texture_pyramid_u8 wrote for the (Ht,Wt,3)
+ * image.  Geometry is untouched: mask, xyz, depth, face and skipped are the bits s6d_raster_views_f32 gives for the same mesh,
+ * poses and camera.  Albedo: the perspective-correct (u, v) of the winning face, wrapped by repeat, sampled bilinearly at ONE
+ * pyramid level L = clamp(floor(log2(rho) + 1/2), 0, Lmax), rho the longer of the two texel-space steps to the samples (u + 1, v)
+ * and (u, v + 1), read from the exponent field of rho^2 (csrc/s6d_raster.hip states every operation); a (u, v) that is not finite
+ * gives albedo 0 and reads no texel.  No gamma, no alpha; shading and rounding as s6d_raster_views_f32.
+ * level (T,H,W) i32 or NULL: the sampled level per pixel, -1 on background (for the tests).
+ * workspace: s6d_raster_workspace_bytes(T, F, H, W) bytes, 8-byte aligned.  Sizes and return codes as s6d_raster_views_f32. */
+int s6d_raster_views_tex_f32(const float *vertices, const int32_t *faces, const float *uv, const void *pyramid, const float *poses,
+                             int V, int F, int T, int H, int W, int Ht, int Wt, float fx, float fy, float cx, float cy, float znear,
+                             float ambient, float diffuse, void *workspace, unsigned char *rgb, unsigned char *mask, float *xyz,
+                             float *depth, int32_t *face, int32_t *level, int32_t *skipped, void *stream);
 
 /* The depth of T views of one mesh alone, a camera per view: poses (T,4,4) f32, cams (T,4) f32 = fx fy cx cy of the view ->
  * depth (T,H,W) f32 camera Z (0 on background), skipped (T) i32.  The vertex stage, the set-up, the coverage rule and the depth

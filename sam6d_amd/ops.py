@@ -722,6 +722,18 @@ def template_ism_crops(images_u8, mask8, params, S, normalize, mean, std):
 
 
 # ------------------------------------------------------------------ template rendering (csrc/s6d_raster.hip)
+def _render_buffers(who, T, F, H, W, dev):
+    """The workspace and the outputs that the two full renders share."""
+    nbytes = _size("s6d_raster_workspace_bytes", T, F, H, W)
+    if nbytes < 0:
+        raise RuntimeError(f"{who}: unsupported sizes (T {T}, F {F}, H {H}, W {W})")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    out = dict(rgb=torch.empty(T, H, W, 3, dtype=torch.uint8, device=dev), mask=torch.empty(T, H, W, dtype=torch.uint8, device=dev),
+               xyz=torch.empty(T, H, W, 3, dtype=torch.float32, device=dev), depth=torch.empty(T, H, W, dtype=torch.float32, device=dev),
+               face=torch.empty(T, H, W, dtype=torch.int32, device=dev), skipped=torch.zeros(T, dtype=torch.int32, device=dev))
+    return ws, out
+
+
 def render_views(vertices, faces, colors, poses, fx, fy, cx, cy, H, W, ambient, diffuse, znear):
     """vertices (V,3) f32, faces (F,3) int32, colors (V,3) uint8, poses (T,4,4) f32 object -> camera (OpenCV axes) ->
     dict(rgb (T,H,W,3) uint8, mask (T,H,W) uint8, xyz (T,H,W,3) f32, depth (T,H,W) f32, face (T,H,W) int32, skipped (T,) int32)
@@ -736,17 +748,54 @@ def render_views(vertices, faces, colors, poses, fx, fy, cx, cy, H, W, ambient, 
                          f"{tuple(faces.shape)}, {tuple(colors.shape)}, {tuple(poses.shape)}")
     if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
         raise ValueError(f"render_views: face indices must lie in [0, {V}), got [{int(faces.min())}, {int(faces.max())}]")
-    nbytes = _size("s6d_raster_workspace_bytes", T, F, H, W)
-    if nbytes < 0:
-        raise RuntimeError(f"render_views: unsupported sizes (T {T}, F {F}, H {H}, W {W})")
-    dev = vertices.device
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    out = dict(rgb=torch.empty(T, H, W, 3, dtype=torch.uint8, device=dev), mask=torch.empty(T, H, W, dtype=torch.uint8, device=dev),
-               xyz=torch.empty(T, H, W, 3, dtype=torch.float32, device=dev), depth=torch.empty(T, H, W, dtype=torch.float32, device=dev),
-               face=torch.empty(T, H, W, dtype=torch.int32, device=dev), skipped=torch.zeros(T, dtype=torch.int32, device=dev))
+    ws, out = _render_buffers("render_views", T, F, H, W, vertices.device)
     _call("s6d_raster_views_f32", _ptr(vertices), _ptr(faces), _ptr(colors), _ptr(poses), V, F, T, H, W, float(fx), float(fy), float(cx),
           float(cy), float(znear), float(ambient), float(diffuse), _ptr(ws), _ptr(out["rgb"]), _ptr(out["mask"]), _ptr(out["xyz"]),
           _ptr(out["depth"]), _ptr(out["face"]), _ptr(out["skipped"]), _stream())
+    return out
+
+
+def texture_pyramid(image):
+    """image (Ht,Wt,3) uint8 RGB, row 0 at the top, 1 <= Ht, Wt <= 8192 -> the box-filtered mip pyramid (N,4) uint8: a texel per
+    row (r, g, b, 0), levels 0 .. floor(log2(max(Wt, Ht))) one after another, level l of max(1, Wt >> l) x max(1, Ht >> l) texels
+    row-major (include/sam6d_hip.h: s6d_texture_pyramid_u8).  Built once per object; ``render_views_textured`` takes it."""
+    _chk(image, torch.uint8, "image", 3)
+    Ht, Wt = image.shape[0], image.shape[1]
+    nbytes = _size("s6d_texture_pyramid_bytes", Ht, Wt)
+    if image.shape[2] != 3 or nbytes < 0:
+        raise ValueError(f"texture_pyramid: image (Ht,Wt,3) with 1 <= Ht, Wt <= 8192 expected, got {tuple(image.shape)}")
+    pyramid = torch.empty(nbytes // 4, 4, dtype=torch.uint8, device=image.device)
+    _call("s6d_texture_pyramid_u8", _ptr(image), Ht, Wt, _ptr(pyramid), _stream())
+    return pyramid
+
+
+def render_views_textured(vertices, faces, uv, pyramid, poses, fx, fy, cx, cy, H, W, ambient, diffuse, znear, tex_size, levels=False):
+    """``render_views`` with a texture in place of the vertex colours: uv (F,3,2) f32 per face corner, pyramid (N,4) uint8 =
+    ``texture_pyramid(image)``, tex_size = (Ht, Wt) of that image.  -> the dict of ``render_views`` (mask, xyz, depth, face and
+    skipped are its bits), with levels=True also ``level`` (T,H,W) int32, the sampled pyramid level, -1 on background
+    (include/sam6d_hip.h: s6d_raster_views_tex_f32).  A face index outside [0, V) is refused here, on the host."""
+    _chk(vertices, torch.float32, "vertices", 2)
+    _chk(faces, torch.int32, "faces", 2)
+    _chk(uv, torch.float32, "uv", 3)
+    _chk(pyramid, torch.uint8, "pyramid", 2)
+    _chk(poses, torch.float32, "poses", 3)
+    V, F, T, H, W = vertices.shape[0], faces.shape[0], poses.shape[0], int(H), int(W)
+    Ht, Wt = (int(s) for s in tex_size)
+    if vertices.shape[1] != 3 or faces.shape[1] != 3 or tuple(uv.shape) != (F, 3, 2) or tuple(poses.shape[1:]) != (4, 4):
+        raise ValueError(f"render_views_textured: vertices (V,3), faces (F,3), uv (F,3,2), poses (T,4,4) expected, got "
+                         f"{tuple(vertices.shape)}, {tuple(faces.shape)}, {tuple(uv.shape)}, {tuple(poses.shape)}")
+    tbytes = _size("s6d_texture_pyramid_bytes", Ht, Wt)
+    if tbytes < 0 or tuple(pyramid.shape) != (tbytes // 4, 4):
+        raise ValueError(f"render_views_textured: tex_size {(Ht, Wt)} must lie in [1, 8192] and pyramid be texture_pyramid's "
+                         f"({max(tbytes, 0) // 4}, 4) for it, got {tuple(pyramid.shape)}")
+    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise ValueError(f"render_views_textured: face indices must lie in [0, {V}), got [{int(faces.min())}, {int(faces.max())}]")
+    ws, out = _render_buffers("render_views_textured", T, F, H, W, vertices.device)
+    if levels:
+        out["level"] = torch.empty(T, H, W, dtype=torch.int32, device=vertices.device)
+    _call("s6d_raster_views_tex_f32", _ptr(vertices), _ptr(faces), _ptr(uv), _ptr(pyramid), _ptr(poses), V, F, T, H, W, Ht, Wt, float(fx),
+          float(fy), float(cx), float(cy), float(znear), float(ambient), float(diffuse), _ptr(ws), _ptr(out["rgb"]), _ptr(out["mask"]),
+          _ptr(out["xyz"]), _ptr(out["depth"]), _ptr(out["face"]), _ptr(out.get("level")), _ptr(out["skipped"]), _stream())
     return out
 
 
@@ -1658,7 +1707,7 @@ def have(name):
                "semantic_select": "s6d_semantic_select_f32", "seq_attention": "s6d_seq_attention_bf16", "sam_preprocess": "s6d_sam_preprocess_f32", "im2col3x3": "s6d_im2col3x3_b16", "nonfinite_rows": "s6d_nonfinite_rows_f32", "patchify": "s6d_patchify_b16", "crop_resize_pad": "s6d_crop_resize_pad_f32", "samdec_img2tok": "s6d_samdec_img2tok_bf16", "samdec_img2tok_raw": "s6d_samdec_img2tok_raw_bf16", "samdec_tok2img": "s6d_samdec_tok2img_f32", "samdec_tok2img_raw": "s6d_samdec_tok2img_raw_bf16", "sam_mask_post": "s6d_sam_mask_post_sel_f32", "gemm_fp8_mx": "s6d_gemm_fp8_mxa", "nms": "s6d_nms_f32", "samdec_upscale_heads": "s6d_samdec_upscale_heads_bf16", "samdec_tokens": "s6d_samdec_tokens_post_bf16", "samdec_token_folds": "s6d_samdec_tokens_post_bf16", "mha": "s6d_mha_f32",
                "linear_attn_focus": "s6d_linear_attn_focus_f32", "linear_attention": "s6d_linear_attention_f32", "project_bbox": "s6d_project_bbox_frames_f32",
                "template_boxes": "s6d_template_boxes_u8", "template_points": "s6d_template_points_f32", "template_pem_crops": "s6d_template_pem_crops_f32",
-               "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32",
+               "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32", "render_views_textured": "s6d_raster_views_tex_f32",
                "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32",
                "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)

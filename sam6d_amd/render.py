@@ -4,13 +4,14 @@ The reference renders its templates off the machine that runs the models: Blende
 the custom flow, pyrender over EGL / OpenGL (``Instance_Segmentation_Model/utils/poses/pyrender.py``) for the BOP flow.  An
 Instinct accelerator has no raster pipeline, so here the views come from a compute rasteriser (csrc/s6d_raster.hip):
 
-    vertices, faces, colors = load_ply(path)
-    onboarded = onboard_from_mesh(descriptor_model, pem_net, [(vertices, faces, colors)], poses, K, (H, W), surface_uniforms=u, keys=k)
+    mesh = load_textured_ply(path)          # (vertices, faces, colors, uv, texture); load_ply for vertex colours alone
+    onboarded = onboard_from_mesh(descriptor_model, pem_net, [mesh], poses, K, (H, W), surface_uniforms=u, keys=k)
     FramePipeline(..., scorer=onboarded.scorer, pem_templates=onboarded.pem_templates, object_radius=onboarded.object_radius)
 
 What is exact and what is defined.  Which pixels a view covers, which face is visible there, the model coordinate of the surface
 point (the reference's ``xyz_i.npy`` / NOCS map) and the depth follow a fixed arithmetic stated in the kernel source.  The COLOUR of
-a path-traced or OpenGL render cannot be reproduced; the shading is a small defined model -- vertex colour times
+a path-traced or OpenGL render cannot be reproduced; the shading is a small defined model -- albedo (vertex colour, or the mesh's
+texture map sampled from a mip pyramid: data, hence part of the definition) times
 ``ambient + diffuse * |n . d|`` with the light at the camera, as in both reference renderers (render_custom_templates.py:67-73,
 pyrender.py:37-43) -- in the way this project defines its samplers instead of imitating a generator.
 
@@ -26,6 +27,9 @@ OpenCV axes with ``tc`` in millimetres; converting them:
     A projection does not see a common scale, so the same views come from the unscaled mesh with ``R = Rc^T`` and
     ``t = -Rc^T tc * 0.004 r`` (model units).
 """
+import collections
+import os
+
 import numpy as np
 import torch
 
@@ -42,11 +46,15 @@ def _device_tensor(a, dtype, name):
 
 
 @torch.no_grad()
-def render_templates(vertices, faces, poses, K, size, colors=None, ambient=0.3, diffuse=0.7, znear=1.0):
+def render_templates(vertices, faces, poses, K, size, colors=None, ambient=0.3, diffuse=0.7, znear=1.0, *, uv=None, texture=None):
     """T views of one mesh.  vertices (V,3) f32 in model units (millimetres for the reference's meshes), faces (F,3) int32,
     poses (T,4,4) f32 object -> camera (OpenCV axes, translation in model units), K the 3 x 3 camera matrix (fx, fy, cx, cy are
     read from it; pixel (u, v) is sampled at its integer coordinate, as K projects), size = (H, W); colors (V,3) uint8 vertex
     colours, None = a uniform grey (``GREY``).  Tensors on the device; numpy arrays are copied there.
+    uv (F,3,2) f32 per face corner and texture (Ht,Wt,3) uint8 RGB, both or neither: the albedo is then the texture, sampled
+    bilinearly from its box-filtered mip pyramid at a per-pixel level (csrc/s6d_raster.hip states it), and ``colors`` plays no
+    part; the geometry outputs are the same bits either way.  The textured render runs on the device kernels only: with them
+    switched off (``policy.disable_fused``) or on host tensors it is refused, never rendered grey.
     ambient / diffuse: the defined shading ``colour * (ambient + diffuse * |n . d|)``; znear in model units (pyrender.py:48 uses
     0.05 m): a triangle with a vertex at Z <= znear is not clipped but refused.
     -> dict: ``rgb`` (T,H,W,3) uint8, ``mask`` (T,H,W) uint8 255 / 0, ``xyz_mm`` (T,H,W,3) f32 model coordinates (0 on background)
@@ -56,12 +64,22 @@ def render_templates(vertices, faces, poses, K, size, colors=None, ambient=0.3, 
     v = _device_tensor(vertices, torch.float32, "vertices")
     f = _device_tensor(faces, torch.int32, "faces")
     p = _device_tensor(poses, torch.float32, "poses")
-    c = torch.full((v.shape[0], 3), GREY, dtype=torch.uint8, device=v.device) if colors is None else _device_tensor(colors, torch.uint8, "colors")
+    if (uv is None) != (texture is None):
+        raise ValueError("render_templates: uv and texture must be given together (got " + ("uv" if texture is None else "texture") + " alone)")
     Km = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64)
     if Km.shape != (3, 3):
         raise ValueError(f"K must be 3 x 3, got {Km.shape}")
     H, W = (int(s) for s in size)
-    out = ops.render_views(v, f, c, p, Km[0, 0], Km[1, 1], Km[0, 2], Km[1, 2], H, W, ambient, diffuse, znear)
+    if uv is None:
+        c = torch.full((v.shape[0], 3), GREY, dtype=torch.uint8, device=v.device) if colors is None else _device_tensor(colors, torch.uint8, "colors")
+        out = ops.render_views(v, f, c, p, Km[0, 0], Km[1, 1], Km[0, 2], Km[1, 2], H, W, ambient, diffuse, znear)
+    else:
+        if not ops.have("render_views_textured"):
+            raise RuntimeError("render_templates: the textured render has no library statement: it needs the device kernel "
+                               "(render_views_textured is switched off by policy.disable_fused or missing from the library)")
+        image = _device_tensor(texture, torch.uint8, "texture")
+        out = ops.render_views_textured(v, f, _device_tensor(uv, torch.float32, "uv"), ops.texture_pyramid(image), p, Km[0, 0], Km[1, 1],
+                                        Km[0, 2], Km[1, 2], H, W, ambient, diffuse, znear, tex_size=image.shape[:2])
     skipped = out["skipped"].cpu()
     if bool(skipped.any()):
         bad = torch.nonzero(skipped).squeeze(1).tolist()
@@ -105,21 +123,78 @@ _PLY_INT = {"char": "<i1", "int8": "<i1", "uchar": "<u1", "uint8": "<u1", "short
             "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4"}
 
 
+_PLY_UV = {"texture_u": 0, "texture_v": 1, "s": 0, "t": 1, "u": 0, "v": 1}          # vertex properties that hold a texture coordinate
+_PLY_VERTEX_LISTS = ("vertex_indices", "vertex_index")
+
+
 def load_ply(path):
     """A triangle mesh from a PLY file -> (vertices (V,3) float32, faces (F,3) int32, colors (V,3) uint8 or None), numpy arrays.
     Formats ``ascii`` and ``binary_little_endian``.  Vertex properties ``x y z``, optionally ``nx ny nz`` (read over) and
     ``red green blue [alpha]``; one face property, the list ``vertex_indices`` (or ``vertex_index``), every face a triangle.
-    Anything else -- another element, property or format, a face that is no triangle -- raises ValueError naming it."""
+    Anything else -- another element, property or format, a face that is no triangle -- raises ValueError naming it
+    (texture coordinates too: ``load_textured_ply`` reads those)."""
+    return _read_ply(path, False)[:3]
+
+
+TexturedMesh = collections.namedtuple("TexturedMesh", "vertices faces colors uv texture")
+
+
+def load_textured_ply(path, texture=None):
+    """``load_ply`` for a mesh whose appearance is a texture map -> TexturedMesh(vertices, faces, colors, uv, texture): uv
+    (F,3,2) float32 per face corner and texture (Ht,Wt,3) uint8 RGB (row 0 at the top), both None for a file without texture
+    coordinates.  On top of ``load_ply``'s properties it reads
+
+      * vertex properties ``texture_u texture_v`` (or ``s t``, or ``u v``), expanded to per-corner values through the faces;
+      * the face list ``texcoord`` of six floats (u, v per corner: MeshLab's wedge coordinates), which wins when both are
+        present, and an optional face property ``texnumber``, 0 throughout;
+      * the image: ``texture`` (a path, or an (Ht,Wt,3) uint8 array) or, without it, the file the single
+        ``comment TextureFile NAME`` names, beside the PLY.  Read with Pillow, ``.convert("RGB")``: no alpha, no gamma.
+
+    ValueError naming the cause: two TextureFile comments, a texcoord list whose length is not 6, a texnumber other than 0,
+    texture coordinates with no image (or an image with no coordinates), a 16-bit image."""
+    vertices, faces, colors, uv, names = _read_ply(path, True)
+    if len(names) > 1:
+        raise ValueError(f"{path}: {len(names)} TextureFile comments ({', '.join(names)}): one texture per mesh is supported")
+    if texture is None and uv is not None and names:
+        texture = os.path.join(os.path.dirname(os.path.abspath(path)), names[0])
+    if uv is None:
+        if texture is not None:
+            raise ValueError(f"{path}: a texture was given but the file has no texture coordinates")
+        return TexturedMesh(vertices, faces, colors, None, None)
+    if texture is None:
+        raise ValueError(f"{path}: texture coordinates but no image (no 'comment TextureFile NAME' in the header and no texture argument)")
+    return TexturedMesh(vertices, faces, colors, uv, _texture_image(texture))
+
+
+def _texture_image(texture):
+    """A path or an array -> (Ht,Wt,3) uint8."""
+    if isinstance(texture, (str, os.PathLike)):
+        from PIL import Image
+        with Image.open(texture) as im:
+            if im.mode.startswith("I") or im.mode == "F":                  # I;16, I;16B, I (what Pillow makes of 16-bit files), F
+                raise ValueError(f"{texture}: image mode '{im.mode}' (16-bit or float) is not supported: 8 bits per channel are read")
+            return np.array(im.convert("RGB"))
+    a = np.asarray(texture.detach().cpu() if torch.is_tensor(texture) else texture)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"texture must be a path or an (Ht,Wt,3) uint8 array, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _read_ply(path, textured):
+    """-> (vertices, faces, colors or None, uv (F,3,2) float32 or None, the names of the TextureFile comments); ``textured``
+    admits the texture properties, which are refused otherwise."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header")
     if not data.startswith(b"ply") or end < 0:
         raise ValueError(f"{path}: not a PLY file")
     body = data[data.index(b"\n", end) + 1:]
-    fmt, elements = None, []
+    fmt, elements, tex_names = None, [], []
     for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
         w = line.split()
         if not w or w[0] in ("comment", "obj_info"):
+            if len(w) > 2 and w[0] == "comment" and w[1] == "TextureFile":
+                tex_names.append(line.split(None, 2)[2].strip())
             continue
         if w[0] == "format":
             fmt = w[1]
@@ -136,7 +211,8 @@ def load_ply(path):
     (_, V, vprops), (_, F, fprops) = elements
     names, fields = [p[-1] for p in vprops], []
     for p in vprops:
-        kind = _PLY_FLOAT if p[-1] in ("x", "y", "z", "nx", "ny", "nz") else _PLY_INT if p[-1] in ("red", "green", "blue", "alpha") else None
+        kind = _PLY_FLOAT if p[-1] in ("x", "y", "z", "nx", "ny", "nz") or (textured and p[-1] in _PLY_UV) else \
+            _PLY_INT if p[-1] in ("red", "green", "blue", "alpha") else None
         if len(p) != 2 or kind is None or p[0] not in kind:
             raise ValueError(f"{path}: unsupported vertex property '{' '.join(p)}'")
         fields.append((p[-1], kind[p[0]]))
@@ -145,50 +221,69 @@ def load_ply(path):
     has_rgb = all(k in names for k in ("red", "green", "blue"))
     if has_rgb and any(dict(fields)[k] != "<u1" for k in ("red", "green", "blue")):
         raise ValueError(f"{path}: unsupported vertex property 'red green blue' of a type other than uchar")
-    if len(fprops) != 1 or len(fprops[0]) != 4 or fprops[0][0] != "list" or fprops[0][3] not in ("vertex_indices", "vertex_index") or \
-            fprops[0][1] not in _PLY_INT or fprops[0][2] not in _PLY_INT:
-        bad = next((p for p in fprops if p[-1] not in ("vertex_indices", "vertex_index")), fprops[0] if fprops else ["(none)"])
-        raise ValueError(f"{path}: unsupported face property '{' '.join(bad)}'")
-    cnt_t, idx_t = _PLY_INT[fprops[0][1]], _PLY_INT[fprops[0][2]]
+    # the face element as a fixed record: (name, dtype of the list's count or None for a scalar, dtype of an item, items)
+    layout = []
+    for p in fprops:
+        if len(p) == 4 and p[0] == "list" and p[3] in _PLY_VERTEX_LISTS and p[1] in _PLY_INT and p[2] in _PLY_INT:
+            layout.append(("faces", _PLY_INT[p[1]], _PLY_INT[p[2]], 3))
+        elif textured and len(p) == 4 and p[0] == "list" and p[3] == "texcoord" and p[1] in _PLY_INT and p[2] in _PLY_FLOAT:
+            layout.append(("texcoord", _PLY_INT[p[1]], _PLY_FLOAT[p[2]], 6))
+        elif textured and len(p) == 2 and p[1] == "texnumber" and p[0] in _PLY_INT:
+            layout.append(("texnumber", None, _PLY_INT[p[0]], 1))
+        else:
+            raise ValueError(f"{path}: unsupported face property '{' '.join(p)}'")
+    if sorted(e[0] for e in layout) != sorted({e[0] for e in layout} | {"faces"}):
+        raise ValueError(f"{path}: unsupported face property '{' '.join(fprops[-1]) if fprops else '(none)'}' (one vertex_indices list, "
+                         "no property twice)")
+    fdt = np.dtype([(n + k, t, s) for n, ct, it, items in layout for k, t, s in ((("#", ct, ()),) if ct else ()) + (("", it, (items,)),)])
     if fmt == "ascii":
         tok = body.split()
         nv = V * len(fields)
         vt = np.array(tok[:nv], dtype=np.float64).reshape(V, len(fields))
         cols = {name: vt[:, i] for i, (name, _) in enumerate(fields)}
-        ft = np.array(tok[nv:], dtype=np.int64)
-        if F and (len(ft) < 1 or ft[0] != 3 or len(ft) != 4 * F or bool((ft.reshape(F, 4)[:, 0] != 3).any())):
-            sizes = _ascii_face_sizes(ft, F)
-            raise ValueError(f"{path}: face size {sizes} is not supported (triangles only)")
-        fa = ft.reshape(F, 4)[:, 1:]
+        ft = np.array(tok[nv:], dtype=np.float64)
+        width = sum(items + (ct is not None) for _, ct, _, items in layout)
+        rows = ft[:len(ft) // width * width].reshape(-1, width)
+        rec, at = {}, 0
+        for n, ct, _, items in layout:
+            if ct:
+                rec[n + "#"], at = rows[:, at], at + 1
+            rec[n], at = rows[:, at:at + items], at + items
+        short = len(ft) != width * F
     else:
         vdt = np.dtype(fields)
         vt = np.frombuffer(body, dtype=vdt, count=V)
         cols = {name: vt[name] for name, _ in fields}
         rest = body[V * vdt.itemsize:]
-        fdt = np.dtype([("n", cnt_t), ("i", idx_t, (3,))])
-        if F and rest[:np.dtype(cnt_t).itemsize] and int(np.frombuffer(rest, dtype=cnt_t, count=1)[0]) != 3:
-            raise ValueError(f"{path}: face size {int(np.frombuffer(rest, dtype=cnt_t, count=1)[0])} is not supported (triangles only)")
-        if len(rest) < F * fdt.itemsize:
-            raise ValueError(f"{path}: truncated face list")
-        ft = np.frombuffer(rest, dtype=fdt, count=F)
-        if bool((ft["n"] != 3).any()):
-            raise ValueError(f"{path}: face size {int(ft['n'][ft['n'] != 3][0])} is not supported (triangles only)")
-        fa = ft["i"]
+        rec = np.frombuffer(rest, dtype=fdt, count=min(F, len(rest) // fdt.itemsize))
+        rec = {n: rec[n] for n in fdt.names}
+        short = len(rest) < F * fdt.itemsize
+    # the first record that is not of the fixed form: everything in front of it was read at the right place
+    bad = [(int(np.argmax(rec[n + "#"] != items)), n, items) for n, ct, _, items in layout if ct and bool((rec[n + "#"] != items).any())]
+    if bad:
+        row, n, items = min(bad)
+        size = int(rec[n + "#"][row])
+        raise ValueError(f"{path}: face size {size} is not supported (triangles only)" if n == "faces" else
+                         f"{path}: texcoord list of length {size} is not supported (6 values: u, v per corner)")
+    if short:
+        raise ValueError(f"{path}: truncated face list" if fmt != "ascii" else f"{path}: face size (truncated list) is not supported (triangles only)")
+    if "texnumber" in rec and bool((rec["texnumber"] != 0).any()):
+        raise ValueError(f"{path}: texnumber {int(rec['texnumber'][rec['texnumber'] != 0][0])}: one texture per mesh is supported (texnumber 0)")
     vertices = np.stack([cols[k] for k in "xyz"], 1).astype(np.float32)
     colors = np.stack([cols[k] for k in ("red", "green", "blue")], 1).astype(np.uint8) if has_rgb else None
-    return vertices, np.ascontiguousarray(fa).astype(np.int32), colors
-
-
-def _ascii_face_sizes(ft, F):
-    """The first face size other than 3 in an ascii face list (for the error message)."""
-    i = 0
-    for _ in range(F):
-        if i >= len(ft):
-            break
-        if ft[i] != 3:
-            return int(ft[i])
-        i += 4
-    return "(truncated list)"
+    faces = np.ascontiguousarray(rec["faces"]).astype(np.int32).reshape(F, 3)
+    uv = None
+    if "texcoord" in rec:
+        uv = np.ascontiguousarray(rec["texcoord"]).astype(np.float32).reshape(F, 3, 2)
+    else:
+        pair = [next((k for k in names if _PLY_UV.get(k) == axis), None) for axis in (0, 1)] if textured else [None, None]
+        if (pair[0] is None) != (pair[1] is None):
+            raise ValueError(f"{path}: vertex property '{pair[0] or pair[1]}' without its partner")
+        if pair[0] is not None:
+            if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+                raise ValueError(f"{path}: face indices must lie in [0, {V})")
+            uv = np.stack([cols[pair[0]], cols[pair[1]]], 1).astype(np.float32)[faces.reshape(-1)].reshape(F, 3, 2)
+    return vertices, faces, colors, uv, tex_names
 
 
 @torch.no_grad()
@@ -196,7 +291,9 @@ def onboard_from_mesh(descriptor_model, pem_net, meshes, poses, K, size, *, surf
                       n_ism_points=2048, unit_scale=1000.0, ambient=0.3, diffuse=0.7, znear=1.0, **onboard_kw):
     """Mesh -> views -> ``onboarding.onboard`` in one process.
 
-    meshes: a list of (vertices (V,3) f32 model units, faces (F,3) int32, colors (V,3) uint8 or None) -- what ``load_ply`` returns;
+    meshes: a list of (vertices (V,3) f32 model units, faces (F,3) int32, colors (V,3) uint8 or None) -- what ``load_ply`` returns
+    -- or of five-element entries (vertices, faces, colors, uv, texture) -- what ``load_textured_ply`` returns: with uv and texture
+    the views carry the texture (``render_templates``), with both None the entry is the three-element one;
     poses (T,4,4) object -> camera, one table for every object (module docstring: converting the reference's tables); K, size,
     ambient, diffuse, znear: ``render_templates``.
     surface_uniforms (O, n_model_points + n_ism_points, 3) in [0, 1): the uniforms of ``sample_surface``, the first n_model_points
@@ -212,10 +309,13 @@ def onboard_from_mesh(descriptor_model, pem_net, meshes, poses, K, size, *, surf
         raise ValueError(f"surface_uniforms must be ({len(meshes)}, {n_m + n_i}, 3), got {tuple(su.shape)}")
     pose_t = _device_tensor(poses, torch.float32, "poses")
     objects = []
-    for o, (vertices, faces, colors) in enumerate(meshes):
+    for o, mesh in enumerate(meshes):
+        if len(mesh) not in (3, 5):
+            raise ValueError(f"meshes[{o}] must have 3 (vertices, faces, colors) or 5 (..., uv, texture) elements, got {len(mesh)}")
+        vertices, faces, colors, uv, texture = tuple(mesh) + (None, None) * (len(mesh) == 3)
         v = _device_tensor(vertices, torch.float32, "vertices")
         f = _device_tensor(faces, torch.int32, "faces")
-        views = render_templates(v, f, pose_t, K, size, colors=colors, ambient=ambient, diffuse=diffuse, znear=znear)
+        views = render_templates(v, f, pose_t, K, size, colors=colors, ambient=ambient, diffuse=diffuse, znear=znear, uv=uv, texture=texture)
         pts = sample_surface(v, f, n_m + n_i, su[o])[0] / torch.full((1,), float(unit_scale), device=v.device)
         objects.append(dict(rgb=views["rgb"], mask=views["mask"], xyz_mm=views["xyz_mm"], model_points=pts[:n_m].contiguous(),
                             ism_points=pts[n_m:].contiguous(), poses=pose_t))

@@ -3,7 +3,7 @@
     python tools/onboard_demo.py [TEMPLATE_DIR]          (on the GPU box)
     python tools/onboard_demo.py --mesh PATH.ply         mesh file -> rendered views -> onboard -> FramePipeline, in this process
 
-With ``--mesh`` the views are rendered on the device (``sam6d_amd.render``: 42 views of 480 x 640 under the LM camera, seeded
+With ``--mesh`` the views are rendered on the device, with the mesh's texture when the file names one (``sam6d_amd.render``: 42 views of 480 x 640 under the LM camera, seeded
 rotations at a distance that lets the object fill about two thirds of the view -- the reference's icosphere pose tables are its
 data and are not shipped), the model / ISM points are ``sample_surface`` draws of the mesh and the whole onboarding is one
 ``onboard_from_mesh`` call.  With a directory of ``rgb_i.png`` / ``mask_i.png`` / ``xyz_i.npy`` the views are read from it (``load_template_dir``); without one, 42
@@ -85,14 +85,14 @@ def mesh_poses(vertices, T=42, seed=0):
 
 def object_from_mesh(path, dev):
     """-> (rgb, mask, xyz numpy views, the object dict of ``onboard``, and the arguments of the equivalent ``onboard_from_mesh`` call)."""
-    vertices, faces, colors = render.load_ply(path)
+    vertices, faces, colors, uv, texture = render.load_textured_ply(path)          # uv, texture: None unless the file names a texture
     poses = mesh_poses(vertices)
-    views = render.render_templates(vertices, faces, poses.to(dev), MESH_K, MESH_SIZE, colors=colors)
+    views = render.render_templates(vertices, faces, poses.to(dev), MESH_K, MESH_SIZE, colors=colors, uv=uv, texture=texture)
     su = torch.rand(1, 1024 + 2048, 3, generator=torch.Generator().manual_seed(4))
     pts = render.sample_surface(torch.from_numpy(vertices), torch.from_numpy(faces), 1024 + 2048, su[0])[0] / torch.full((1,), 1000.0)
     rgb, mask, xyz = (views[k].cpu().numpy() for k in ("rgb", "mask", "xyz_mm"))
     obj = dict(rgb=rgb, mask=mask, xyz_mm=xyz, model_points=pts[:1024].numpy(), ism_points=pts[1024:].numpy(), poses=poses.numpy())
-    return rgb, mask, xyz, obj, dict(meshes=[(vertices, faces, colors)], poses=poses.to(dev), surface_uniforms=su)
+    return rgb, mask, xyz, obj, dict(meshes=[(vertices, faces, colors, uv, texture)], poses=poses.to(dev), surface_uniforms=su)
 
 
 def models(dev):
@@ -129,9 +129,10 @@ def main():
     d_rgb, d_mask, d_xyz = (torch.from_numpy(a).to(dev) for a in (rgb, mask, xyz))
     res = dict(views=T, height=H, width=W, n_sample=5000, img_size=224)
     if mesh:
-        v, f, c = mesh_args["meshes"][0]
-        res.update(mesh=os.path.basename(mesh), vertices=len(v), faces=len(f), covered_pixels_per_view=int((mask == 255).sum()) // T)
-        res["render_ms"], _ = timed(lambda: render.render_templates(v, f, mesh_args["poses"], MESH_K, MESH_SIZE, colors=c))
+        v, f, c, uv, tex = mesh_args["meshes"][0]
+        res.update(mesh=os.path.basename(mesh), vertices=len(v), faces=len(f), covered_pixels_per_view=int((mask == 255).sum()) // T,
+                   texture=None if tex is None else list(tex.shape[:2]))
+        res["render_ms"], _ = timed(lambda: render.render_templates(v, f, mesh_args["poses"], MESH_K, MESH_SIZE, colors=c, uv=uv, texture=tex))
         res["onboard_ms"], onb = timed(lambda: render.onboard_from_mesh(dino, net, mesh_args["meshes"], mesh_args["poses"], MESH_K, MESH_SIZE,
                                                                         surface_uniforms=mesh_args["surface_uniforms"], keys=keys, n_view=T))
         ref = onboarding.onboard(dino, net, [obj], keys=keys, n_view=T)

@@ -5,10 +5,13 @@ python tools/stage_times.py --geo-ab [result.json]   the geo_embedding stage alo
 python tools/stage_times.py --coarse-sim-ab [result.json]   the step from the out_proj outputs to atten alone (pm.feature_similarity), policy
                                                      field coarse_sim "0" / "1" alternating in this process at 32 and 10 instances (quoted
                                                      in profiles/coarse_similarity.md)
-python tools/stage_times.py --render [result.json]   ops.render_views alone: 42 views of 480 x 640 of a 45,600-face torus (one lane per
-                                                     triangle) and of a 12-face cube (a workgroup per triangle), beside the time of
-                                                     one device copy of the key buffer -- its bytes read once and written once at the
-                                                     copy rate, the floor of the visibility pass (quoted in profiles/render.md)
+python tools/stage_times.py --render [result.json [OTHER.so]]   ops.render_views and ops.render_views_textured (2048 x 2048 texture)
+                                                     alone: 42 views of 480 x 640 of a 45,600-face torus (one lane per
+                                                     triangle) and of a 12-face cube (a workgroup per triangle), the pyramid build,
+                                                     beside the time of one device copy of the key buffer -- its bytes read once and
+                                                     written once at the copy rate, the floor of the visibility pass; with OTHER.so
+                                                     (the parent commit's library) ops.render_views through both builds, alternating
+                                                     (quoted in profiles/render.md)
 python tools/stage_times.py --bop-eval [result.json]   the BOP pose errors (sam6d_amd.evaluation): kernels beside the library statements in
                                                      this process -- MSSD / MSPD of 256 estimates, 20,000 vertices, 1 and 315 symmetries;
                                                      the two depth renders and the pixel stage of VSD at 480 x 640 with 10 taus --
@@ -170,14 +173,19 @@ def coarse_sim_ab(path=None, rounds=9, calls=50):
         print(json.dumps(out))
 
 
-def render_times(path=None, rounds=5, calls=200):
-    """ops.render_views on the two work shapes at the reference's template size (42 views, 480 x 640, the LM camera of
-    Instance_Segmentation_Model/utils/poses/pyrender.py:88-91): device-event times per call (workspace allocation and the face-index
-    check of the wrapper included), the covered pixels, the triangles the workgroup kernel took, and the copy of the key buffer."""
+def render_times(path=None, rounds=5, calls=200, other=None):
+    """ops.render_views and ops.render_views_textured (a 2048 x 2048 texture) on the two work shapes at the reference's template
+    size (42 views, 480 x 640, the LM camera of Instance_Segmentation_Model/utils/poses/pyrender.py:88-91): device-event times per
+    call (workspace allocation and the face-index check of the wrapper included), the covered pixels, the triangles the workgroup
+    kernel took, the pyramid build and the copy of the key buffer.  other: the library of another build (the parent commit's):
+    ops.render_views through both in alternating rounds, and whether the outputs are equal."""
+    import ctypes
+
     import numpy as np
 
-    from sam6d_amd import ops
+    from sam6d_amd import _lib, ops
     from tests import render_ref as R
+    from tests import texture_ref as X
     T, H, W = 42, 480, 640
     K = (572.4114, 573.57043, 325.2611, 242.04899)
     out = {"views": T, "height": H, "width": W, "rounds": rounds, "calls_per_round": calls, "device": torch.cuda.get_device_name(0)}
@@ -197,15 +205,41 @@ def render_times(path=None, rounds=5, calls=200):
         out[f"key_buffer_copy_{key}_ms"] = rows
         out[f"key_buffer_copy_{key}_median_ms"] = statistics.median(rows)
         out[f"copy_rate_{key}_GBps"] = round(2 * out["key_buffer_bytes"] / statistics.median(rows) / 1e6, 1)
-    del pairs[1:]
-    for name, (v, f, c), z in (("torus_45600_faces", R.torus(152, 150), 300.0), ("cube_12_faces", R.cube(), 300.0)):
-        P = R.poses(T, seed=1, t=(0.0, 0.0, z))
-        tv, tf, tc, tp = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (v, f, c, P))
+    del pairs[:]
+    image = torch.from_numpy(X.texture(2048, 2048, 1)).cuda()
+    rows = [round(_event_ms(lambda: ops.texture_pyramid(image), 50), 4) for _ in range(rounds)]
+    out["texture_pyramid_2048_ms"], out["texture_pyramid_2048_median_ms"] = rows, statistics.median(rows)
+    pyramid = ops.texture_pyramid(image)
+    libs = {"this": _lib.lib()}
+    if other:
+        libs["other"] = ctypes.CDLL(other)
+    meshes = (("torus_45600_faces", R.torus(152, 150), lambda f: X.expand(X.torus_uv(152, 150), f)), ("cube_12_faces", R.cube(), lambda f: X.cube_uv()))
+    for name, (v, f, c), uv_of in meshes:
+        P = R.poses(T, seed=1, t=(0.0, 0.0, 300.0))
+        tv, tf, tc, tp, tu = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (v, f, c, P, uv_of(f)))
         step = lambda: ops.render_views(tv, tf, tc, tp, *K, H, W, 0.3, 0.7, 1.0)  # noqa: E731
-        rows = [round(_event_ms(step, calls), 4) for _ in range(rounds)]
-        res = step()
-        r = {"faces": int(tf.shape[0]), "ms": rows, "median_ms": statistics.median(rows), "covered_pixels_per_view": int((res["mask"] == 255).sum()) // T,
-             "skipped": int(res["skipped"].sum()), "launches": _launches(step)}
+        tex = lambda: ops.render_views_textured(tv, tf, tu, pyramid, tp, *K, H, W, 0.3, 0.7, 1.0, tex_size=(2048, 2048))  # noqa: E731
+        ms, res = {k: [] for k in libs}, {}
+        try:
+            for r in range(rounds + 1):                              # round 0 warms every build up
+                for k in sorted(libs):
+                    _lib._lib = libs[k]
+                    t = _event_ms(step, calls)
+                    if r:
+                        ms[k].append(round(t, 4))
+                    res[k] = step()
+        finally:
+            _lib._lib = libs["this"]
+        rows_tex = [round(_event_ms(tex, calls), 4) for _ in range(rounds)]
+        got = tex()
+        r = {"faces": int(tf.shape[0]), "ms": ms["this"], "median_ms": statistics.median(ms["this"]), "textured_ms": rows_tex,
+             "textured_median_ms": statistics.median(rows_tex), "covered_pixels_per_view": int((res["this"]["mask"] == 255).sum()) // T,
+             "skipped": int(res["this"]["skipped"].sum()), "launches": _launches(step), "textured_launches": _launches(tex),
+             "textured_geometry_equal": all(bool(torch.equal(got[k], res["this"][k])) for k in ("mask", "xyz", "depth", "face", "skipped"))}
+        if other:
+            r.update(other_ms=ms["other"], other_median_ms=statistics.median(ms["other"]),
+                     ratio_of_medians=round(statistics.median(ms["this"]) / statistics.median(ms["other"]), 4),
+                     outputs_equal_other=all(bool(torch.equal(res["this"][k], res["other"][k])) for k in res["this"]))
         print(name, r, flush=True)
         out[name] = r
     if path:
@@ -337,7 +371,7 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--bop-eval":
         bop_eval_times(sys.argv[2] if len(sys.argv) > 2 else None)
     elif len(sys.argv) > 1 and sys.argv[1] == "--render":
-        render_times(sys.argv[2] if len(sys.argv) > 2 else None)
+        render_times(sys.argv[2] if len(sys.argv) > 2 else None, other=sys.argv[3] if len(sys.argv) > 3 else None)
     elif len(sys.argv) > 1 and sys.argv[1] == "--geo-ab":
         geo_ab(sys.argv[2] if len(sys.argv) > 2 else None)
     elif len(sys.argv) > 2 and sys.argv[1] == "--fine-match-ab":
