@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 132
+#define S6D_ABI_VERSION 133
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -890,6 +890,38 @@ int s6d_sam_mask_post_sel_f32(const float *low_res, int B, int ch_total, int ch_
 int s6d_nms_f32(const float *boxes, const int64_t *order, int N, float iou_threshold, void *workspace,
                 unsigned char *keep_sorted, void *stream);
 long s6d_nms_workspace_bytes(int N);
+
+/* Connected components and the small-region clean-up of SAM's automatic mask generator (min_mask_region_area > 0), csrc/s6d_ccl.hip.
+ * masks (N,H,W) bytes, a pixel is SET when its byte is not 0; connectivity is 8 everywhere; H W < 2^31.
+ *
+ * s6d_label_components_u8: labels (N,H,W) i32.  With background = 0 the components of the set pixels, with background = 1 those of
+ * the unset pixels: the label of such a pixel is the row-major index y W + x of the FIRST pixel of its component (the component's
+ * minimum index, inside its own mask), -1 on the pixels of the other polarity.
+ *
+ * s6d_remove_small_regions_u8 (min_area >= 1), the DEFINITION:
+ *   1. holes: of the components of the UNSET pixels, every one with area < min_area is set -- one that touches the image border
+ *      like any other.  changed_h = there was such a component.
+ *   2. islands, on the result of 1: the components of the SET pixels with area < min_area are small.  None: nothing happens.  Small
+ *      and non-small ones: the small ones are cleared.  Every component small: only the one of largest area stays, among equal areas
+ *      the one whose first pixel in row-major order comes first.  changed_i = there was a small component (also when the pixels end
+ *      up as they were: one component, small).
+ *   3. changed[n] = changed_h or changed_i (0 / 1); min_area = 1 changes nothing (the comparison is strict).
+ *   4. out (N,H,W) bytes 0 / 1 (also valid as a bool tensor); boxes (N,4) i32 XYXY of out with an inclusive maximum corner,
+ *      (0,0,0,0) for an empty mask.
+ * Everything is integer arithmetic: the results do not depend on scheduling, on N or on how a caller cuts N into chunks.  `out` must
+ * not alias `masks`.  workspace: s6d_small_regions_workspace_bytes(N, H, W) bytes for either entry (-1 for sizes the entries refuse),
+ * 8-byte aligned.  Tiles of S6D_CCL_TILE_H x S6D_CCL_TILE_W pixels are labelled in LDS and joined across their borders in global memory.
+ * Returns S6D_EINVAL for NULL operands, non-positive H / W, negative N, H W >= 2^31 or min_area < 1, before any launch; N = 0: S6D_OK.
+ * ref: remove_small_regions, segment_anything/utils/amg.py:267-291 (cv2.connectedComponentsWithStats(..., 8): an un-vendored
+ * dependency whose label numbering -- the tie in step 2 -- is not restated; the rule above is this project's definition);
+ * batched_mask_to_box :303-346. */
+#define S6D_CCL_TILE_H 16
+#define S6D_CCL_TILE_W 64
+long s6d_small_regions_workspace_bytes(int N, int H, int W);
+int s6d_label_components_u8(const uint8_t *masks, int N, int H, int W, int background, void *workspace, int32_t *labels,
+                            void *stream);
+int s6d_remove_small_regions_u8(const uint8_t *masks, int N, int H, int W, long min_area, void *workspace, uint8_t *out,
+                                uint8_t *changed, int32_t *boxes, void *stream);
 
 #ifdef __cplusplus
 }

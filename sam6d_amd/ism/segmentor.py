@@ -10,8 +10,12 @@ kernels behind it).  Same constructor arguments, same return value: ``{"masks": 
 and integer XYXY boxes without ``segmentor_width_size``, float masks (bilinear, not re-thresholded) and float boxes
 with it, exactly as the reference returns them.
 
-Not provided: ``min_mask_region_area > 0`` (postprocess_small_regions: cv2 connected components, an un-vendored dependency;
-the ISM configuration sets 0) and crop layers (``crop_n_layers`` is 0 in the reference's generator as the ISM builds it).
+Not provided BY THIS CLASS: ``min_mask_region_area > 0``.  The reference's class fails on that path too -- its ``_generate_masks``
+returns a plain dict and ``postprocess_small_regions`` then indexes ``mask_data["rles"]`` (model/sam.py:108-116, 146-148): a
+``KeyError`` -- and the ISM configuration sets 0, so the constructor keeps refusing it.  The option itself (upstream's
+``postprocess_small_regions``, connected components on the device) lives in ``amg.generate_proposals(min_mask_region_area=)`` and
+``FramePipeline(segmentor={"min_mask_region_area": k})``.  Not provided at all: crop layers (``crop_n_layers`` is 0 in the
+reference's generator as the ISM builds it).
 When the frame is not ``segmentor_width_size`` wide the reference shrinks it with ``cv2.resize``; here Pillow's bilinear
 resampler (sam/transforms.py) does it -- same filter, possibly different rounding; for 640-wide frames it is the identity.
 """
@@ -37,8 +41,10 @@ class CustomSamAutomaticMaskGenerator:
     def __init__(self, sam, min_mask_region_area=0, points_per_batch=64, stability_score_thresh=0.85, box_nms_thresh=0.7,
                  crop_overlap_ratio=512 / 1500, segmentor_width_size=None, pred_iou_thresh=0.88):
         if min_mask_region_area > 0:
-            raise NotImplementedError("min_mask_region_area > 0 needs cv2 connected components (postprocess_small_regions); "
-                                      "the ISM configuration uses 0")
+            raise NotImplementedError("min_mask_region_area > 0 is not served by this class: the reference's class fails there too "
+                                      "(KeyError: its plain dict has no 'rles', model/sam.py:108-116, 146-148) and the ISM "
+                                      "configuration uses 0; use amg.generate_proposals(min_mask_region_area=) or "
+                                      "FramePipeline(segmentor={'min_mask_region_area': k})")
         self.sam = sam
         self.points_per_batch = points_per_batch
         self.stability_score_thresh = stability_score_thresh

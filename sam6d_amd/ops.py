@@ -965,6 +965,57 @@ def coco_match(ious, iou_off, groups, det_area, gt_area, gt_ignore, thresholds, 
     return match, ignore
 
 
+# ------------------------------------------------------------------ connected components / small mask regions (csrc/s6d_ccl.hip)
+SMALL_REGIONS_WORKSPACE_BYTES = 512 << 20      # masks go through the kernels in chunks whose workspace (two int32 planes) stays under this
+CCL_TILE = (_lib.header_constant("S6D_CCL_TILE_H"), _lib.header_constant("S6D_CCL_TILE_W"))
+
+
+def _binary_masks(masks, what):
+    if masks.dtype == torch.bool and masks.is_cuda and masks.is_contiguous():
+        masks = masks.view(torch.uint8)
+    _chk(masks, torch.uint8, "masks", 3)
+    N, H, W = masks.shape
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"{what}: masks (N,H,W) with 1 <= H W < 2^31 expected, got {tuple(masks.shape)}")
+    per_mask = _size("s6d_small_regions_workspace_bytes", 1, H, W)
+    return masks, max(1, SMALL_REGIONS_WORKSPACE_BYTES // per_mask)
+
+
+def label_components(masks, background=False):
+    """masks (N,H,W) uint8 or bool (non-zero = set) -> labels (N,H,W) int32: the 8-connected components of the set pixels (of the
+    unset ones with ``background``); a pixel's label is the row-major index of the first pixel of its component, -1 on the other
+    polarity (include/sam6d_hip.h: s6d_label_components_u8).  Processed in chunks of masks; a mask's labels do not depend on them."""
+    masks, chunk = _binary_masks(masks, "label_components")
+    N, H, W = masks.shape
+    labels = torch.empty(N, H, W, dtype=torch.int32, device=masks.device)
+    for a in range(0, N, chunk):
+        n = min(chunk, N - a)
+        ws = torch.empty(_size("s6d_small_regions_workspace_bytes", n, H, W), dtype=torch.uint8, device=masks.device)
+        _call("s6d_label_components_u8", _ptr(masks[a:a + n]), n, H, W, int(bool(background)), _ptr(ws), _ptr(labels[a:a + n]), _stream())
+    return labels
+
+
+def remove_small_regions(masks, min_area):
+    """masks (N,H,W) uint8 or bool, min_area >= 1 -> (masks (N,H,W) uint8 0 / 1, changed (N,) bool, boxes (N,4) int32 XYXY, inclusive
+    maximum corner, zeros for an empty mask): holes (components of unset pixels) with area < min_area filled, then islands with
+    area < min_area removed -- the largest kept when all are small (include/sam6d_hip.h: s6d_remove_small_regions_u8).  Processed in
+    chunks of masks; a mask's result does not depend on them."""
+    masks, chunk = _binary_masks(masks, "remove_small_regions")
+    if int(min_area) != min_area or min_area < 1:
+        raise ValueError(f"remove_small_regions: min_area must be an integer >= 1, got {min_area!r}")
+    N, H, W = masks.shape
+    dev = masks.device
+    out = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
+    changed = torch.empty(N, dtype=torch.bool, device=dev)
+    boxes = torch.empty(N, 4, dtype=torch.int32, device=dev)
+    for a in range(0, N, chunk):
+        n = min(chunk, N - a)
+        ws = torch.empty(_size("s6d_small_regions_workspace_bytes", n, H, W), dtype=torch.uint8, device=dev)
+        _call("s6d_remove_small_regions_u8", _ptr(masks[a:a + n]), n, H, W, int(min_area), _ptr(ws), _ptr(out[a:a + n]),
+              _ptr(changed[a:a + n]), _ptr(boxes[a:a + n]), _stream())
+    return out, changed, boxes
+
+
 def upsample_gather(up, choose, H, W, C):
     """up (B,196,16*C) f32, choose (B,n) int64 -> (B,n,C): bilinear x4 of the pixel-shuffled map at chosen pixels."""
     _chk(up, torch.float32, "up", 3)
@@ -1709,7 +1760,8 @@ def have(name):
                "template_boxes": "s6d_template_boxes_u8", "template_points": "s6d_template_points_f32", "template_pem_crops": "s6d_template_pem_crops_f32",
                "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32", "render_views_textured": "s6d_raster_views_tex_f32",
                "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32",
-               "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match"}.get(name)
+               "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match",
+               "small_regions": "s6d_remove_small_regions_u8"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):

@@ -36,7 +36,8 @@ class FramePipeline:
         """descriptor_model: sam6d_amd.ism.dinov2.CustomDINOv2; scorer: sam6d_amd.ism.scoring.FrameScorer (holds the
         template descriptors); pem_templates: dict(dense_po (O,n,3), dense_fo (O,n,C), model (O,m,3)) of the O objects (O = 1: every detection
         is that object; O > 1: rows are picked by the ISM's predicted object id); object_radius: a number or an (O,) tensor;
-        segmentor: keyword overrides of amg.generate_proposals (thresholds).  nms_per_object_thresh: the BOP flow's
+        segmentor: keyword overrides of amg.generate_proposals (thresholds; ``{"min_mask_region_area": k}`` fills holes and drops
+        islands below k pixels and reruns the box NMS, amg.postprocess_small_regions).  nms_per_object_thresh: the BOP flow's
         ``apply_nms_per_object_id`` after scoring (detector.py:388-390; 0.25 in configs/model/ISM_sam.yaml; the custom
         demo flow has none).  det_score_thresh: only detections scoring above it go to the PEM
         (run_inference_custom.py:165-171, default 0.2 there); top_k=None keeps every detection, top_k="keys" keeps as many per
