@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 133
+#define S6D_ABI_VERSION 134
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -922,6 +922,44 @@ int s6d_label_components_u8(const uint8_t *masks, int N, int H, int W, int backg
                             void *stream);
 int s6d_remove_small_regions_u8(const uint8_t *masks, int N, int H, int W, long min_area, void *workspace, uint8_t *out,
                                 uint8_t *changed, int32_t *boxes, void *stream);
+
+/* Run-length masks (csrc/s6d_rle.hip): the uncompressed, column-major run lists of the BOP / COCO detection
+ * json (ref: mask_to_rle, Instance_Segmentation_Model/model/utils.py:24-43; rle_to_mask, Pose_Estimation_Model/utils/data_utils.py:72-89).
+ *
+ * Pixel order of the runs: p = x H + y, 0 <= p < H W.  The runs of a mask are c[0 .. k): c[0] zeros (possibly 0 long), c[1] ones,
+ * alternating.  CANONICAL (what the encoder writes): k >= 1, c[i] >= 1 for i >= 1, sum c = H W; an all-zero mask is [H W], an
+ * all-one mask [0, H W].  A batch: counts (R) i32, offsets (N + 1) i64 non-decreasing with offsets[0] = 0, offsets[N] = R, the list
+ * of mask n being counts[offsets[n] .. offsets[n + 1]).  1 <= H W < 2^31, N >= 0.
+ *
+ * Encoder, two entries.  s6d_rle_count_u8: masks (N,H,W) bytes (not 0 = set) -> run_counts (N) i32 = k of every mask, and per-band
+ * transition counts in `workspace` (s6d_rle_encode_workspace_bytes(N, H, W) bytes, -1 for sizes the entries refuse).  The caller makes
+ * offsets = the exclusive scan of run_counts, R = their sum, and s6d_rle_write_u8 with the SAME masks and workspace (and the same
+ * s6d_set_rle_band_words setting) fills counts (R) i32 in position order; edges (R) i32 is scratch.  A store that would leave a
+ * mask's [offsets[n], offsets[n + 1]) is dropped.
+ *
+ * Decoders.  They accept any list with c[i] >= 0 and sum c = H W (zero-length runs anywhere).  ends (R) i64 = the INCLUSIVE scan of
+ * counts over the whole batch (a run's start inside its mask is ends[i - 1] - ends[offsets[n] - 1]).  status (N + 1) i32, written:
+ * status[1 + n] = 1 when mask n has a negative count, an empty list or a total != H W; status[0] = the first such n, or 2^31 - 1.
+ * Nothing is promised about the outputs of a refused mask; the other masks are complete.
+ *   s6d_rle_to_packed   -> packed (N, ceil(H W / 64)) 64-bit words and area (N) i32 exactly as s6d_mask_pack_u8 makes them from
+ *                          the dense mask (bit k of word j = ROW-major pixel 64 j + k, bits past H W zero).  Every word and area is
+ *                          written; no dense mask exists anywhere.
+ *   s6d_rle_to_masks_u8 -> masks (N,H,W) bytes 0 / 1, every byte written.
+ * One workgroup per (mask, band of columns); a band is kept in LDS as column-major bits, at most S6D_RLE_BAND_WORDS 64-bit words
+ * (a column takes ceil(H / 64) | 1 of them: S6D_EUNSUPPORTED when one column does not fit).  s6d_set_rle_band_words(w) lowers that
+ * capacity (0 < w <= S6D_RLE_BAND_WORDS; 0 = the default) so that tests cross band seams at small shapes: same results for every
+ * setting.  Process-wide; not to be changed between s6d_rle_count_u8 and s6d_rle_write_u8.
+ * Every entry returns S6D_EINVAL for NULL operands, H or W < 1, N < 0, H W >= 2^31 or R < N before any launch; N = 0: S6D_OK. */
+#define S6D_RLE_BAND_WORDS 4096
+int s6d_set_rle_band_words(int words);
+long s6d_rle_encode_workspace_bytes(int N, int H, int W);
+int s6d_rle_count_u8(const uint8_t *masks, int N, int H, int W, void *workspace, int32_t *run_counts, void *stream);
+int s6d_rle_write_u8(const uint8_t *masks, int N, int H, int W, void *workspace, const long *offsets, long R, int32_t *edges,
+                     int32_t *counts, void *stream);
+int s6d_rle_to_packed(const int32_t *counts, const long *offsets, const long *ends, int N, long R, int H, int W, int32_t *status,
+                      uint64_t *packed, int32_t *area, void *stream);
+int s6d_rle_to_masks_u8(const int32_t *counts, const long *offsets, const long *ends, int N, long R, int H, int W, int32_t *status,
+                        uint8_t *masks, void *stream);
 
 #ifdef __cplusplus
 }

@@ -449,17 +449,43 @@ def _mask_counts_library(dm, gm, pairs, chunk_bytes=1 << 28):
     return (torch.cat(inter) if inter else torch.zeros(0, dtype=torch.int32, device=dm.device)), da, ga
 
 
+def _is_rle(m):
+    from .ism import handoff
+    return isinstance(m, handoff.RleMasks)
+
+
+def _mask_operand(m, dev):
+    """Masks for the counts: run lists (``handoff.RleMasks``) moved to dev as they are, everything else dense (N,H,W) uint8 on dev."""
+    return m.to(dev) if _is_rle(m) else _masks_u8(m, dev)
+
+
+def _mask_shape(m):
+    return (len(m),) + tuple(m.size) if _is_rle(m) else tuple(m.shape)
+
+
+def _mask_areas(m, dev):
+    """Set pixels of every mask -> (N,) float64 on dev."""
+    m = _mask_operand(m, dev)
+    if _is_rle(m):
+        return m.packed()[1].double()
+    return m.flatten(1).ne(0).sum(1).double()
+
+
 def _mask_counts(det_masks, gt_masks, pairs, device=None, site="eval.mask_ious"):
-    dev = _coco_device(device, det_masks, gt_masks)
-    dm, gm = _masks_u8(det_masks, dev), _masks_u8(gt_masks, dev)
-    if tuple(dm.shape[1:]) != tuple(gm.shape[1:]) and dm.shape[0] and gm.shape[0]:
-        raise ValueError(f"detection masks are {tuple(dm.shape[1:])}, ground-truth masks {tuple(gm.shape[1:])}")
-    p = _pairs_i32(pairs, dev, dm.shape[0], gm.shape[0])
-    if dm.shape[1] * dm.shape[2] >= 1 and gm.shape[1] * gm.shape[2] >= 1 and _coco_kernels(site, dm, "mask_pack", "mask_pair_inter"):
-        dp, da = ops.mask_pack(dm)
-        gp, ga = ops.mask_pack(gm)
+    dev = _coco_device(device, *(m.counts if _is_rle(m) else m for m in (det_masks, gt_masks)))
+    dm, gm = _mask_operand(det_masks, dev), _mask_operand(gt_masks, dev)
+    ds, gs = _mask_shape(dm), _mask_shape(gm)
+    if ds[1:] != gs[1:] and ds[0] and gs[0]:
+        raise ValueError(f"detection masks are {ds[1:]}, ground-truth masks {gs[1:]}")
+    p = _pairs_i32(pairs, dev, ds[0], gs[0])
+    need = ["mask_pair_inter"] + ([] if _is_rle(dm) and _is_rle(gm) else ["mask_pack"])
+    if ds[1] * ds[2] >= 1 and gs[1] * gs[2] >= 1 and _coco_kernels(site, p if _is_rle(dm) else dm, *need):
+        # run lists go straight to the packed words (``RleMasks.packed``: ops.rle_to_packed), dense masks through ops.mask_pack
+        dp, da = dm.packed() if _is_rle(dm) else ops.mask_pack(dm)
+        gp, ga = gm.packed() if _is_rle(gm) else ops.mask_pack(gm)
         inter = ops.mask_pair_inter(dp, gp, p) if p.shape[0] else torch.zeros(0, dtype=torch.int32, device=dev)
         return inter, da, ga, p
+    dm, gm = (m.to_dense().view(torch.uint8) if _is_rle(m) else m for m in (dm, gm))
     return _mask_counts_library(dm, gm, p) + (p,)
 
 
@@ -474,7 +500,8 @@ def mask_ious(det_masks, gt_masks, pairs, device=None):
     """IoU of P (detection, ground truth) mask pairs -> (P,) float64 on the device.  det_masks (Nd,H,W), gt_masks (Ng,H,W) bool or
     uint8 (non-zero = set), pairs (P,2) rows into them.  inter = popcount(d & g), union = |d| + |g| - inter, integers;
     iou = double(inter) / double(union), 0 for an empty union.  Kernels on device tensors (``ops.mask_pack``, ``ops.mask_pair_inter``),
-    the dense torch statement (``_mask_counts_library``) on CPU tensors or when ``policy.disable_fused`` names a kernel."""
+    the dense torch statement (``_mask_counts_library``) on CPU tensors or when ``policy.disable_fused`` names a kernel.  Either side
+    may be a ``handoff.RleMasks``: its run lists are packed by ``ops.rle_to_packed`` without a dense mask; same counts."""
     return _iou_from_counts(*_mask_counts(det_masks, gt_masks, pairs, device))
 
 
@@ -600,10 +627,14 @@ def coco_match(ious, iou_off, groups, det_area, gt_area, gt_ignore, thresholds=C
     return _coco_match_library(v, off, gr, da, ga, gf, th, ar)
 
 
-def detections_from_records(records):
+def detections_from_records(records, masks="dense", device=None):
     """The records of a BOP result file (``handoff.detection_records`` / ``read_bop_json``) -> the ``detections`` of ``coco_scores``:
-    im (n,2) = (scene_id, image_id), category, score, bbox (n,4) x y w h float64, masks (n,H,W) bool (when every record has one)."""
+    im (n,2) = (scene_id, image_id), category, score, bbox (n,4) x y w h float64, masks (when every record has one): with
+    ``masks="dense"`` (n,H,W) bool on the host, decoded one record at a time; with ``masks="rle"`` a ``handoff.RleMasks`` on
+    ``device`` (default: the host) -- the run lists as they are in the file, one flat array, never a dense mask."""
     from .ism import handoff
+    if masks not in ("dense", "rle"):
+        raise ValueError(f"masks must be 'dense' or 'rle', got {masks!r}")
     n = len(records)
     out = dict(im=np.array([[int(r["scene_id"]), int(r["image_id"])] for r in records], np.int64).reshape(n, 2),
                category=np.array([int(r["category_id"]) for r in records], np.int64),
@@ -614,7 +645,10 @@ def detections_from_records(records):
             if isinstance(r["segmentation"].get("counts"), (str, bytes)):
                 raise ValueError("the segmentation of a record is a COMPRESSED RLE string: only uncompressed run-length lists "
                                  "(what save_json_bop23 writes) are read")
-        out["masks"] = np.stack([handoff.rle_to_mask(r["segmentation"]) for r in records])
+        if masks == "rle":
+            out["masks"] = handoff.RleMasks.from_records([r["segmentation"] for r in records], device)
+        else:
+            out["masks"] = np.stack([handoff.rle_to_mask(r["segmentation"]) for r in records])
     return out
 
 
@@ -653,7 +687,8 @@ def _mean(a):
 def coco_scores(detections, ground_truths, iou_type="segm", device=None):
     """COCO AP / AR of detections against ground truths, by the DEFINITION below (``iou_type`` "segm": mask IoU, "bbox": box IoU).
 
-    detections: dict(im, category, score, masks (D,H,W) | bbox (D,4) x y w h) -- the masks may be dense device tensors --, or a
+    detections: dict(im, category, score, masks (D,H,W) | bbox (D,4) x y w h) -- the masks may be dense device tensors, or run
+    lists (``handoff.RleMasks``, on either side or both: the same result dict as with the dense masks) --, or a
     batch of ``handoff.Detections``, or the records of a result file (``read_bop_json``).  ground_truths: dict(im, category,
     masks (G,H,W) visible masks, bbox (G,4) visible boxes (bbox only), ignore (G,), optionally area (G,) instead of masks for
     bbox).  ``im`` is (n,) or (n,k) integers (k = 2: scene, image); a group is one (im, category).
@@ -675,7 +710,8 @@ def coco_scores(detections, ground_truths, iou_type="segm", device=None):
     if iou_type not in ("segm", "bbox"):
         raise ValueError(f"iou_type must be 'segm' or 'bbox', got {iou_type!r}")
     det, gt = _as_detections(detections), ground_truths
-    dev = _coco_device(device, det.get("masks") if iou_type == "segm" else None)
+    d_masks = det.get("masks") if iou_type == "segm" else None
+    dev = _coco_device(device, d_masks.counts if _is_rle(d_masks) else d_masks)
     key = lambda x, n: np.asarray(torch.as_tensor(x).cpu() if torch.is_tensor(x) else x, np.int64).reshape(n, -1)
     d_score = np.asarray(torch.as_tensor(det["score"]).cpu() if torch.is_tensor(det["score"]) else det["score"], np.float64).reshape(-1)
     D, G = d_score.shape[0], np.asarray(gt["category"]).reshape(-1).shape[0]
@@ -711,8 +747,8 @@ def coco_scores(detections, ground_truths, iou_type="segm", device=None):
             d_area, g_area = da.double(), ga.double()
         else:
             iou = torch.zeros(0, dtype=torch.float64, device=dev)
-            d_area = _masks_u8(det["masks"], dev).flatten(1).ne(0).sum(1).double() if D else torch.zeros(0, dtype=torch.float64, device=dev)
-            g_area = _masks_u8(gt["masks"], dev).flatten(1).ne(0).sum(1).double() if G else torch.zeros(0, dtype=torch.float64, device=dev)
+            d_area = _mask_areas(det["masks"], dev) if D else torch.zeros(0, dtype=torch.float64, device=dev)
+            g_area = _mask_areas(gt["masks"], dev) if G else torch.zeros(0, dtype=torch.float64, device=dev)
     else:
         db = torch.as_tensor(det["bbox"]).detach().to(device=dev, dtype=torch.float64).reshape(-1, 4)
         iou = box_ious(db, gt["bbox"], pairs, dev) if D and G else torch.zeros(0, dtype=torch.float64, device=dev)
@@ -720,7 +756,7 @@ def coco_scores(detections, ground_truths, iou_type="segm", device=None):
         if gt.get("area") is not None:
             g_area = torch.as_tensor(gt["area"]).detach().to(device=dev, dtype=torch.float64).reshape(-1)
         else:
-            g_area = _masks_u8(gt["masks"], dev).flatten(1).ne(0).sum(1).double() if G else torch.zeros(0, dtype=torch.float64, device=dev)
+            g_area = _mask_areas(gt["masks"], dev) if G else torch.zeros(0, dtype=torch.float64, device=dev)
     idx = lambda a: torch.as_tensor(a, device=dev)
     k_area, s_area = d_area[idx(kd)] if len(kd) else d_area[:0], g_area[idx(go)] if G else g_area[:0]
     s_ign = g_ign[go]
@@ -768,17 +804,18 @@ def coco_scores(detections, ground_truths, iou_type="segm", device=None):
             "ground_truths": int(G), "ignored": int(g_ign.sum()), "groups": int(NG)}
 
 
-def read_bop_json(path):
+def read_bop_json(path, masks="dense", device=None):
     """The records ``ism.handoff.save_json_bop23`` writes (a JSON list of scene_id, image_id, category_id, bbox x y w h, score, time,
     segmentation = {"counts": run lengths in column-major order, "size": [H, W]}) -> dict(scene, im, category (n,) int64,
     score (n,) float64, bbox (n,4) float64, time (n,) float64, masks (n,H,W) bool or None when the records carry none), the masks
-    decoded through ``handoff.rle_to_mask``.  A ``counts`` that is a compressed RLE STRING is refused: only the uncompressed lists are
+    decoded through ``handoff.rle_to_mask``; with ``masks="rle"`` they stay run lists, a ``handoff.RleMasks`` on ``device``
+    (``coco_scores`` takes either).  A ``counts`` that is a compressed RLE STRING is refused: only the uncompressed lists are
     read."""
     import json
     with open(path) as f:
         records = json.load(f)
     if not isinstance(records, list):
         raise ValueError(f"{path}: a JSON list of detection records expected")
-    d = detections_from_records(records)
+    d = detections_from_records(records, masks, device)
     return dict(scene=d["im"][:, 0].copy(), im=d["im"][:, 1].copy(), category=d["category"], score=d["score"], bbox=d["bbox"],
                 time=np.array([float(r.get("time", -1.0)) for r in records], np.float64), masks=d.get("masks"))

@@ -1016,6 +1016,99 @@ def remove_small_regions(masks, min_area):
     return out, changed, boxes
 
 
+# ------------------------------------------------------------------ run-length masks (csrc/s6d_rle.hip)
+RLE_BAND_WORDS = _lib.header_constant("S6D_RLE_BAND_WORDS")
+_RLE_OK = 2 ** 31 - 1
+
+
+def set_rle_band_words(words):
+    """LDS capacity of a column band of the run-length kernels in 64-bit words, 0 = the default (include/sam6d_hip.h:
+    s6d_set_rle_band_words): lets tests cross band seams at small shapes; same results for every setting."""
+    _call("s6d_set_rle_band_words", int(words))
+
+
+def rle_encode(masks):
+    """masks (N,H,W) uint8 or bool (non-zero = set) -> (counts (R,) int32, offsets (N+1,) int64): the canonical column-major run
+    lists of every mask, the list of mask n being counts[offsets[n]:offsets[n+1]] (include/sam6d_hip.h: s6d_rle_count_u8,
+    s6d_rle_write_u8).  The exclusive scan of the per-mask run counts between the two kernels is ``torch.cumsum``."""
+    if masks.dtype == torch.bool and masks.is_cuda and masks.is_contiguous():
+        masks = masks.view(torch.uint8)
+    _chk(masks, torch.uint8, "masks", 3)
+    N, H, W = masks.shape
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"rle_encode: masks (N,H,W) with 1 <= H W < 2^31 expected, got {tuple(masks.shape)}")
+    dev = masks.device
+    offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    if N == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev), offsets
+    nbytes = _size("s6d_rle_encode_workspace_bytes", N, H, W)
+    if nbytes < 0:
+        raise ValueError(f"rle_encode: s6d_rle_encode_workspace_bytes refuses N = {N}, H = {H}, W = {W} (a column of H pixels must fit "
+                         f"the band capacity, 64 pixels per word)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    runs =torch.empty(N, dtype=torch.int32, device=dev)
+    _call("s6d_rle_count_u8", _ptr(masks), N, H, W, _ptr(ws), _ptr(runs), _stream())
+    torch.cumsum(runs, 0, dtype=torch.int64, out=offsets[1:])
+    R = int(offsets[-1])
+    edges = torch.empty(R, dtype=torch.int32, device=dev)
+    counts = torch.empty(R, dtype=torch.int32, device=dev)
+    _call("s6d_rle_write_u8", _ptr(masks), N, H, W, _ptr(ws), _ptr(offsets), R, _ptr(edges), _ptr(counts), _stream())
+    return counts, offsets
+
+
+def _rle_operands(counts, offsets, H, W, what):
+    _chk(counts, torch.int32, "counts", 1)
+    _chk(offsets, torch.int64, "offsets", 1)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"{what}: 1 <= H W < 2^31 expected, got H = {H}, W = {W}")
+    N, R = offsets.shape[0] - 1, counts.shape[0]
+    if N < 0:
+        raise ValueError(f"{what}: offsets (N+1,) expected, got {tuple(offsets.shape)}")
+    o = offsets.cpu()
+    if int(o[0]) != 0 or int(o[-1]) != R or (N and bool((o[1:] < o[:-1]).any())):
+        raise ValueError(f"{what}: offsets must be non-decreasing from 0 to len(counts) = {R}, got {int(o[0])} .. {int(o[-1])}")
+    if N and bool((o[1:] == o[:-1]).any()):
+        raise ValueError(f"{what}: mask {int(torch.nonzero(o[1:] == o[:-1])[0, 0])} has an empty run list")
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)                     # the run starts: a library scan (DESIGN section 14)
+    status = torch.empty(N + 1, dtype=torch.int32, device=counts.device)
+    return N, R, H, W, ends, status
+
+
+def _rle_refusal(status, what, H, W):
+    bad = int(status[0])
+    if bad != _RLE_OK:
+        raise ValueError(f"{what}: mask {bad} is not a run list of {H} x {W} pixels (a negative count, or the counts do not sum to "
+                         f"{H * W})")
+
+
+def rle_to_packed(counts, offsets, H, W):
+    """counts (R,) int32, offsets (N+1,) int64, run lists in column-major order -> (packed (N, ceil(H W / 64)) int64, area (N,)
+    int32), exactly ``mask_pack`` of the dense masks, which are never made (include/sam6d_hip.h: s6d_rle_to_packed).  Zero-length
+    runs are accepted anywhere; a negative count, an empty list or a total other than H W raises ValueError naming the first such
+    mask."""
+    N, R, H, W, ends, status = _rle_operands(counts, offsets, H, W, "rle_to_packed")
+    packed = torch.empty(N, (H * W + 63) // 64, dtype=torch.int64, device=counts.device)
+    area = torch.empty(N, dtype=torch.int32, device=counts.device)
+    if N == 0:
+        return packed, area
+    _call("s6d_rle_to_packed", _ptr(counts), _ptr(offsets), _ptr(ends), N, R, H, W, _ptr(status), _ptr(packed), _ptr(area), _stream())
+    _rle_refusal(status, "rle_to_packed", H, W)
+    return packed, area
+
+
+def rle_to_masks(counts, offsets, H, W):
+    """counts (R,) int32, offsets (N+1,) int64 -> dense masks (N,H,W) uint8 0 / 1 (include/sam6d_hip.h: s6d_rle_to_masks_u8); accepts
+    and refuses what ``rle_to_packed`` does."""
+    N, R, H, W, ends, status = _rle_operands(counts, offsets, H, W, "rle_to_masks")
+    masks = torch.empty(N, H, W, dtype=torch.uint8, device=counts.device)
+    if N == 0:
+        return masks
+    _call("s6d_rle_to_masks_u8", _ptr(counts), _ptr(offsets), _ptr(ends), N, R, H, W, _ptr(status), _ptr(masks), _stream())
+    _rle_refusal(status, "rle_to_masks", H, W)
+    return masks
+
+
 def upsample_gather(up, choose, H, W, C):
     """up (B,196,16*C) f32, choose (B,n) int64 -> (B,n,C): bilinear x4 of the pixel-shuffled map at chosen pixels."""
     _chk(up, torch.float32, "up", 3)
@@ -1761,7 +1854,8 @@ def have(name):
                "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32", "render_views_textured": "s6d_raster_views_tex_f32",
                "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32",
                "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match",
-               "small_regions": "s6d_remove_small_regions_u8"}.get(name)
+               "small_regions": "s6d_remove_small_regions_u8",
+               "rle_encode": "s6d_rle_write_u8", "rle_to_packed": "s6d_rle_to_packed", "rle_to_masks": "s6d_rle_to_masks_u8"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):

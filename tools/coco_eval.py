@@ -1,6 +1,6 @@
 """Score an ISM result file with sam6d_amd.evaluation.coco_scores (COCO AP / AR of the BOP 2D detection and segmentation tasks):
 
-python tools/coco_eval.py --results X.json --dataset DIR [--split test] [--iou-type segm|bbox] [--device cuda|cpu]
+python tools/coco_eval.py --results X.json --dataset DIR [--split test] [--iou-type segm|bbox] [--device cuda|cpu] [--masks dense|rle]
 
 X.json: the records ``ism.handoff.save_json_bop23`` writes (scene_id, image_id, category_id, bbox x y w h, score, time, segmentation =
 uncompressed column-major RLE).  DIR: a dataset in the BOP layout, walked as tools/bop_eval.py walks it --
@@ -8,7 +8,8 @@ uncompressed column-major RLE).  DIR: a dataset in the BOP layout, walked as too
   DIR/<split>/<scene:06d>/scene_gt_info.json     bbox_visib (x y w h) and visib_fract: an instance below 0.1 is IGNORED, not dropped
   DIR/<split>/<scene:06d>/mask_visib/<im:06d>_<j:06d>.png      the visible mask of instance j (non-zero = set)
 Every image named in the ground truth of the scenes the result file covers is scored (test_targets_*.json is not read).  Prints
-one JSON line.
+one JSON line.  --masks rle: the results stay run lists (``handoff.RleMasks``) and the mask_visib PNGs are encoded to run lists on the
+device RLE_CHUNK at a time, so the host never holds more than one chunk of dense masks; the same line as --masks dense.
 
 pycocotools and bop_toolkit are not part of this project: the numbers follow the definition in sam6d_amd/evaluation.py (DESIGN
 section 12), and no equality with another tool's output is claimed."""
@@ -24,8 +25,12 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def load_ground_truth(root, split, scenes, min_visib=None):
-    """-> (ground_truths dict(im (G,2) = scene, image; category, masks (G,H,W) bool, bbox (G,4), ignore), images {(scene, im)})."""
+RLE_CHUNK = 256                                   # mask_visib PNGs held dense at a time under --masks rle
+
+
+def load_ground_truth(root, split, scenes, min_visib=None, masks="dense", device=None):
+    """-> (ground_truths dict(im (G,2) = scene, image; category, masks (G,H,W) bool, bbox (G,4), ignore), images {(scene, im)}).
+    masks="rle": the masks are a ``handoff.RleMasks`` on ``device``, encoded RLE_CHUNK PNGs at a time."""
     from PIL import Image
 
     from bop_eval import walk_scenes
@@ -33,6 +38,15 @@ def load_ground_truth(root, split, scenes, min_visib=None):
     min_visib = evaluation.COCO_MIN_VISIB if min_visib is None else min_visib
     gt = dict(im=[], category=[], masks=[], bbox=[], ignore=[])
     images = set()
+    parts, shapes = [], set()
+
+    def flush():
+        import torch
+
+        from sam6d_amd.ism import handoff
+        if gt["masks"]:
+            parts.append(handoff.RleMasks.from_masks(torch.from_numpy(np.stack(gt["masks"])).to(device or "cpu")))
+            gt["masks"].clear()
     for scene, im, d, records, gt_info, _ in walk_scenes(root, split, scenes):
         if gt_info is None:
             raise FileNotFoundError(f"{d}/scene_gt_info.json is needed (bbox_visib, visib_fract)")
@@ -43,12 +57,20 @@ def load_ground_truth(root, split, scenes, min_visib=None):
             gt["masks"].append(np.asarray(Image.open(os.path.join(d, "mask_visib", f"{im:06d}_{j:06d}.png"))) != 0)
             gt["bbox"].append([float(v) for v in gt_info[j]["bbox_visib"]])
             gt["ignore"].append(float(gt_info[j]["visib_fract"]) < min_visib)
-    if len({m.shape for m in gt["masks"]}) > 1:
-        raise ValueError(f"visible masks of different sizes: {sorted({m.shape for m in gt['masks']})}")
-    n = len(gt["masks"])
+            shapes.add(gt["masks"][-1].shape)
+            if len(shapes) > 1:
+                raise ValueError(f"visible masks of different sizes: {sorted(shapes)}")
+            if masks == "rle" and len(gt["masks"]) >= RLE_CHUNK:
+                flush()
+    n = len(gt["category"])
+    if masks == "rle" and n:
+        from sam6d_amd.ism import handoff
+        flush()
+        dense = handoff.RleMasks.cat(parts)
+    else:
+        dense = np.stack(gt["masks"]) if n else np.zeros((0, 1, 1), bool)
     return dict(im=np.asarray(gt["im"], np.int64).reshape(n, 2), category=np.asarray(gt["category"], np.int64),
-                masks=np.stack(gt["masks"]) if n else np.zeros((0, 1, 1), bool), bbox=np.asarray(gt["bbox"], np.float64).reshape(n, 4),
-                ignore=np.asarray(gt["ignore"], bool)), images
+                masks=dense, bbox=np.asarray(gt["bbox"], np.float64).reshape(n, 4), ignore=np.asarray(gt["ignore"], bool)), images
 
 
 def main(argv=None):
@@ -58,20 +80,22 @@ def main(argv=None):
     ap.add_argument("--split", default="test")
     ap.add_argument("--iou-type", default="segm", choices=("segm", "bbox"))
     ap.add_argument("--device", default=None, help="cuda (kernels) or cpu (the torch statements); default: cuda when there is one")
+    ap.add_argument("--masks", default="dense", choices=("dense", "rle"),
+                    help="rle: results and ground truth stay run lists, packed on the device without dense masks; same output")
     a = ap.parse_args(argv)
     import torch
 
     from sam6d_amd import evaluation
     t0 = time.time()
-    res = evaluation.read_bop_json(a.results)
-    gt, images = load_ground_truth(a.dataset, a.split, set(res["scene"].tolist()))
+    device = a.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    res = evaluation.read_bop_json(a.results, masks=a.masks, device=device if a.masks == "rle" else None)
+    gt, images = load_ground_truth(a.dataset, a.split, set(res["scene"].tolist()), masks=a.masks, device=device)
     keep = np.array([(int(s), int(i)) in images for s, i in zip(res["scene"], res["im"])], bool)
     if a.iou_type == "segm" and res["masks"] is None and keep.any():
         raise ValueError(f"{a.results}: the records carry no segmentation; use --iou-type bbox")
     det = dict(im=np.stack([res["scene"], res["im"]], 1)[keep], category=res["category"][keep], score=res["score"][keep], bbox=res["bbox"][keep])
     if res["masks"] is not None:
         det["masks"] = res["masks"][keep]
-    device = a.device or ("cuda" if torch.cuda.is_available() else "cpu")
     out = evaluation.coco_scores(det, gt, a.iou_type, device=device)
     out.update(results=os.path.basename(a.results), images=len(images), dropped_detections=int((~keep).sum()), seconds=round(time.time() - t0, 3))
     print(json.dumps(out))
