@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 134
+#define S6D_ABI_VERSION 135
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -960,6 +960,39 @@ int s6d_rle_to_packed(const int32_t *counts, const long *offsets, const long *en
                       uint64_t *packed, int32_t *area, void *stream);
 int s6d_rle_to_masks_u8(const int32_t *counts, const long *offsets, const long *ends, int N, long R, int H, int W, int32_t *status,
                         uint8_t *masks, void *stream);
+
+/* Pose refinement against the measured depth (csrc/s6d_refine.hip): one Gauss-Newton step of projective
+ * point-to-plane ICP for T instances of one mesh.  SAM-6D has no refinement (no ref): the step is this project's DEFINITION, stated
+ * operation by operation in the header of csrc/s6d_refine.hip -- float64 formed from the float32 inputs, one rounding per operation,
+ * a fixed reduction order, no floating-point atomics: an instance has the same bits alone and in a batch.
+ *
+ * s6d_refine_normal_eq_f64: xyz (T,H,W,3) f32 model coordinates and face (T,H,W) i32 of s6d_raster_views_f32 at poses (T,4,4) f32
+ * (object -> camera, translation in model units); depth_obs (M,H,W) f32 measured depth, depth_unit model units per unit of it (<= 0
+ * or not finite = missing); obs_index (T) i32 into M; mask (T,H,W) bytes (0 = leave out) or NULL; vertices (V,3) f32, faces (F,3) i32
+ * -> sums (T,28) f64 = the 21 upper entries of J J^T row-major, the 6 of J r, and r r, summed over the correspondences, and
+ * count (T) i32.  A pixel is a correspondence when its face index lies in [0, F) (and the face's vertex indices in [0, V)), the
+ * mask is set, the depth positive, the face not degenerate, |cos| of the angle between its normal and the viewing ray >= min_cos
+ * and the measured point within max_dist (model units) of the rendered one.  An obs_index outside [0, M) leaves the instance at
+ * zeros.  A workgroup sums S6D_RF_CHUNK consecutive pixels; workspace: s6d_refine_workspace_bytes(T, H, W) bytes, 8-byte aligned
+ * (-1 for sizes the entry refuses).
+ *
+ * s6d_refine_update_f64: solves (S A S + damping I) y = S b by Cholesky with Jacobi scaling S = diag(A_ii^-1/2), xi = S y, and
+ * applies xi = (omega, v) by the Cayley map: R' = dR R, t' = dR t + v -> poses_out (T,4,4) f32, status (T) i32, rms (T) f64 =
+ * sqrt(sum r r / count).  status 0 = updated, 1 = count < min_count, 2 = a Cholesky pivot below min_pivot (the visible surface
+ * leaves a direction free), 3 = a sum or a pose that is not finite.  Any non-zero status copies the input pose bit for bit.
+ * poses_out must not alias poses.
+ *
+ * Both return S6D_EINVAL for NULL operands (mask excepted), V, F, M, H or W < 1, T < 0, fx or fy zero or NaN, depth_unit <= 0,
+ * max_dist negative or not finite, min_cos outside [0, 1], min_count < 1, damping negative or min_pivot <= 0 (or not finite), and
+ * S6D_EUNSUPPORTED for H W >= 2^31 or T x chunks >= 2^31, before any launch; T = 0: S6D_OK. */
+#define S6D_RF_CHUNK 1024
+long s6d_refine_workspace_bytes(int T, int H, int W);
+int s6d_refine_normal_eq_f64(const float *xyz, const int32_t *face, const float *depth_obs, const int32_t *obs_index,
+                             const uint8_t *mask, const float *vertices, const int32_t *faces, const float *poses, int V, int F, int T,
+                             int M, int H, int W, float fx, float fy, float cx, float cy, float depth_unit, float max_dist,
+                             float min_cos, void *workspace, double *sums, int32_t *count, void *stream);
+int s6d_refine_update_f64(const double *sums, const int32_t *count, const float *poses, int T, int min_count, float damping,
+                          float min_pivot, float *poses_out, int32_t *status, double *rms, void *stream);
 
 #ifdef __cplusplus
 }

@@ -734,10 +734,11 @@ def _render_buffers(who, T, F, H, W, dev):
     return ws, out
 
 
-def render_views(vertices, faces, colors, poses, fx, fy, cx, cy, H, W, ambient, diffuse, znear):
+def render_views(vertices, faces, colors, poses, fx, fy, cx, cy, H, W, ambient, diffuse, znear, check_faces=True):
     """vertices (V,3) f32, faces (F,3) int32, colors (V,3) uint8, poses (T,4,4) f32 object -> camera (OpenCV axes) ->
     dict(rgb (T,H,W,3) uint8, mask (T,H,W) uint8, xyz (T,H,W,3) f32, depth (T,H,W) f32, face (T,H,W) int32, skipped (T,) int32)
-    for all T views (include/sam6d_hip.h: s6d_raster_views_f32).  A face index outside [0, V) is refused here, on the host."""
+    for all T views (include/sam6d_hip.h: s6d_raster_views_f32).  A face index outside [0, V) is refused here, on the host;
+    check_faces=False is for a caller that has made that check on the same faces already (it reads the device: a synchronisation)."""
     _chk(vertices, torch.float32, "vertices", 2)
     _chk(faces, torch.int32, "faces", 2)
     _chk(colors, torch.uint8, "colors", 2)
@@ -746,7 +747,7 @@ def render_views(vertices, faces, colors, poses, fx, fy, cx, cy, H, W, ambient, 
     if vertices.shape[1] != 3 or faces.shape[1] != 3 or tuple(colors.shape) != (V, 3) or tuple(poses.shape[1:]) != (4, 4):
         raise ValueError(f"render_views: vertices (V,3), faces (F,3), colors (V,3), poses (T,4,4) expected, got {tuple(vertices.shape)}, "
                          f"{tuple(faces.shape)}, {tuple(colors.shape)}, {tuple(poses.shape)}")
-    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+    if check_faces and F and (int(faces.min()) < 0 or int(faces.max()) >= V):
         raise ValueError(f"render_views: face indices must lie in [0, {V}), got [{int(faces.min())}, {int(faces.max())}]")
     ws, out = _render_buffers("render_views", T, F, H, W, vertices.device)
     _call("s6d_raster_views_f32", _ptr(vertices), _ptr(faces), _ptr(colors), _ptr(poses), V, F, T, H, W, float(fx), float(fy), float(cx),
@@ -872,6 +873,70 @@ def vsd_counts(depth_est, depth_gt, depth_test, test_index, cams, delta, taus, s
     _call("s6d_vsd_counts_f32", _ptr(depth_est), _ptr(depth_gt), _ptr(depth_test), _ptr(test_index), _ptr(cams), _ptr(scale), N, M, H, W,
           float(delta), (ctypes.c_float * max(NT, 1))(*tau), NT, _ptr(union), _ptr(inter), _ptr(ge), _stream())
     return union, inter, ge
+
+
+# ------------------------------------------------------------------ pose refinement against the depth (csrc/s6d_refine.hip)
+RF_CHUNK = _lib.header_constant("S6D_RF_CHUNK")          # pixels one workgroup of the normal-equation kernel sums (its reduction order)
+RF_TERMS = 28                                            # 21 upper entries of J J^T, 6 of J r, r r
+
+
+def refine_normal_eq(xyz, face, depth_obs, obs_index, mask, vertices, faces, poses, fx, fy, cx, cy, depth_unit, max_dist, min_cos,
+                     check_index=True):
+    """xyz (T,H,W,3) f32 and face (T,H,W) int32 of ``render_views`` at poses (T,4,4) f32, depth_obs (M,H,W) f32, obs_index (T,) int32
+    into M, mask (T,H,W) uint8 or None, vertices (V,3) f32, faces (F,3) int32 -> (sums (T,28) f64, count (T,) int32): the normal
+    equations of one point-to-plane step (include/sam6d_hip.h: s6d_refine_normal_eq_f64).  An obs_index outside [0, M) is refused
+    here, on the host; check_index=False leaves that read of the device out (the kernel then gives such an instance zeros)."""
+    _chk(xyz, torch.float32, "xyz", 4)
+    _chk(face, torch.int32, "face", 3)
+    _chk(depth_obs, torch.float32, "depth_obs", 3)
+    _chk(obs_index, torch.int32, "obs_index", 1)
+    _chk(vertices, torch.float32, "vertices", 2)
+    _chk(faces, torch.int32, "faces", 2)
+    _chk(poses, torch.float32, "poses", 3)
+    if mask is not None:
+        _chk(mask, torch.uint8, "mask", 3)
+    T, H, W = face.shape
+    M, V, F = depth_obs.shape[0], vertices.shape[0], faces.shape[0]
+    if tuple(xyz.shape) != (T, H, W, 3) or tuple(depth_obs.shape[1:]) != (H, W) or tuple(obs_index.shape) != (T,) or \
+            tuple(poses.shape) != (T, 4, 4) or vertices.shape[1] != 3 or faces.shape[1] != 3 or \
+            (mask is not None and tuple(mask.shape) != (T, H, W)):
+        raise ValueError(f"refine_normal_eq: xyz (T,H,W,3), face (T,H,W), depth_obs (M,H,W), obs_index (T,), mask (T,H,W), vertices (V,3), "
+                         f"faces (F,3), poses (T,4,4) expected, got {tuple(xyz.shape)}, {tuple(face.shape)}, {tuple(depth_obs.shape)}, "
+                         f"{tuple(obs_index.shape)}, {None if mask is None else tuple(mask.shape)}, {tuple(vertices.shape)}, "
+                         f"{tuple(faces.shape)}, {tuple(poses.shape)}")
+    if check_index and T and (int(obs_index.min()) < 0 or int(obs_index.max()) >= M):
+        raise ValueError(f"refine_normal_eq: obs_index must lie in [0, {M}), got [{int(obs_index.min())}, {int(obs_index.max())}]")
+    nbytes = _size("s6d_refine_workspace_bytes", T, H, W)
+    if nbytes < 0:
+        raise RuntimeError(f"refine_normal_eq: unsupported sizes (T {T}, H {H}, W {W})")
+    dev = xyz.device
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    sums = torch.empty(T, RF_TERMS, dtype=torch.float64, device=dev)
+    count = torch.empty(T, dtype=torch.int32, device=dev)
+    _call("s6d_refine_normal_eq_f64", _ptr(xyz), _ptr(face), _ptr(depth_obs), _ptr(obs_index), _ptr(mask), _ptr(vertices), _ptr(faces),
+          _ptr(poses), V, F, T, M, H, W, float(fx), float(fy), float(cx), float(cy), float(depth_unit), float(max_dist), float(min_cos),
+          _ptr(ws), _ptr(sums), _ptr(count), _stream())
+    return sums, count
+
+
+def refine_update(sums, count, poses, min_count, damping, min_pivot):
+    """sums (T,28) f64 and count (T,) int32 of ``refine_normal_eq``, poses (T,4,4) f32 -> (poses_out (T,4,4) f32, status (T,) int32,
+    rms (T,) f64): the damped, Jacobi-scaled Cholesky solve and the Cayley update (include/sam6d_hip.h: s6d_refine_update_f64).
+    status 0 updated, 1 too few correspondences, 2 singular, 3 not finite; a non-zero status returns the input pose."""
+    _chk(sums, torch.float64, "sums", 2)
+    _chk(count, torch.int32, "count", 1)
+    _chk(poses, torch.float32, "poses", 3)
+    T = poses.shape[0]
+    if tuple(sums.shape) != (T, RF_TERMS) or tuple(count.shape) != (T,) or tuple(poses.shape[1:]) != (4, 4):
+        raise ValueError(f"refine_update: sums (T,28), count (T,), poses (T,4,4) expected, got {tuple(sums.shape)}, {tuple(count.shape)}, "
+                         f"{tuple(poses.shape)}")
+    dev = poses.device
+    out = torch.empty_like(poses)
+    status = torch.empty(T, dtype=torch.int32, device=dev)
+    rms = torch.empty(T, dtype=torch.float64, device=dev)
+    _call("s6d_refine_update_f64", _ptr(sums), _ptr(count), _ptr(poses), T, int(min_count), float(damping), float(min_pivot), _ptr(out),
+          _ptr(status), _ptr(rms), _stream())
+    return out, status, rms
 
 
 # ------------------------------------------------------------------ COCO AP of ISM results (csrc/s6d_cocoeval.hip)
@@ -1855,7 +1920,8 @@ def have(name):
                "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32",
                "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match",
                "small_regions": "s6d_remove_small_regions_u8",
-               "rle_encode": "s6d_rle_write_u8", "rle_to_packed": "s6d_rle_to_packed", "rle_to_masks": "s6d_rle_to_masks_u8"}.get(name)
+               "rle_encode": "s6d_rle_write_u8", "rle_to_packed": "s6d_rle_to_packed", "rle_to_masks": "s6d_rle_to_masks_u8",
+               "refine_normal_eq": "s6d_refine_normal_eq_f64", "refine_update": "s6d_refine_update_f64"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):

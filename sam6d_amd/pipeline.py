@@ -32,7 +32,7 @@ from .sam.transforms import ResizeLongestSide
 class FramePipeline:
     def __init__(self, sam_encoder, prompt_encoder, mask_decoder, descriptor_model, scorer, pem_net, pem_templates,
                  object_radius, top_k=10, points_per_batch=1024, min_box_size=0.05 ** 2, min_mask_size=3e-4,
-                 segmentor=None, nms_per_object_thresh=None, det_score_thresh=None, sync_stages=True):
+                 segmentor=None, nms_per_object_thresh=None, det_score_thresh=None, sync_stages=True, refiner=None):
         """descriptor_model: sam6d_amd.ism.dinov2.CustomDINOv2; scorer: sam6d_amd.ism.scoring.FrameScorer (holds the
         template descriptors); pem_templates: dict(dense_po (O,n,3), dense_fo (O,n,C), model (O,m,3)) of the O objects (O = 1: every detection
         is that object; O > 1: rows are picked by the ISM's predicted object id); object_radius: a number or an (O,) tensor;
@@ -55,6 +55,7 @@ class FramePipeline:
         self.nms_thresh, self.det_thresh = nms_per_object_thresh, det_score_thresh
         self.times = {}
         self.sync_stages = sync_stages
+        self.refiner = refiner
         self.graph_max = int(policy.current().pem_graph_max)      # instance counts up to this one replay a captured graph
         self._pem_graphs = {}
         # a captured graph bakes the weights' addresses and derived buffers in: the fingerprint in _pem_graph_key sees version bumps and
@@ -283,17 +284,44 @@ class FramePipeline:
         ep = dict(pts=cat("pts"), rgb=cat("rgb"), rgb_choose=cat("rgb_choose"), model=tpl("model"), dense_po=tpl("dense_po"),
                   dense_fo=tpl("dense_fo"), coarse_rand_u=ru_l[0] if len(ru_l) == 1 else torch.cat(ru_l))
         out = self._pem_forward(ep)
-        self._tick("pem", t0)
+        t0 = self._tick("pem", t0)
+        if self.refiner is not None:
+            out = self._refine(out, dets, frames, count, obs_l, oid if multi else None)
+            self._tick("pem_refine", t0)
+        extra = [key for key in ("pred_R_pem", "pred_t_pem", "refine_status", "refine_rms") if key in out]
         res, at, k = [], 0, 0
         for det, n in zip(dets, count):
             if n == 0:
                 res.append((det, None))
                 continue
             res.append((det, dict(pred_R=out["pred_R"][at:at + n], pred_t=out["pred_t"][at:at + n],
-                                  pred_pose_score=out["pred_pose_score"][at:at + n], kept=obs_l[k]["kept"])))
+                                  pred_pose_score=out["pred_pose_score"][at:at + n], kept=obs_l[k]["kept"],
+                                  **{key: out[key][at:at + n] for key in extra})))
             at += n
             k += 1
         return res
+
+    def _refine(self, out, dets, frames, count, obs_l, oid):
+        """The PEM's poses of the group pulled onto each frame's own depth map (pem/refine.py): per frame one call of the refiner
+        with that frame's depth and camera, the instances' object ids (oid, None = one object) and -- ``refiner.use_masks`` -- the
+        kept detections' masks.  -> ``out`` with the refined pose under pred_R / pred_t, the PEM's own under pred_R_pem /
+        pred_t_pem, and refine_status / refine_rms per instance.  The refiner converts units itself (``depth_unit``: this class
+        works in metres, the meshes usually in millimetres)."""
+        R, t = out["pred_R"].float().clone(), out["pred_t"].float().clone()
+        status = torch.zeros(R.shape[0], dtype=torch.int32, device=R.device)
+        rms = torch.zeros(R.shape[0], dtype=torch.float64, device=R.device)
+        at, k = 0, 0
+        for det, frame, n in zip(dets, frames, count):
+            if n == 0:
+                continue
+            sl = slice(at, at + n)
+            masks = det.masks[obs_l[k]["kept"]] if getattr(self.refiner, "use_masks", False) else None
+            ref = self.refiner([0] * n if oid is None else oid[sl], R[sl].contiguous(), t[sl].contiguous(), frame[1].float(), frame[2],
+                               masks=masks)
+            R[sl], t[sl], status[sl], rms[sl] = ref["R"], ref["t"], ref["status"], ref["rms"]
+            at += n
+            k += 1
+        return dict(out, pred_R=R, pred_t=t, pred_R_pem=out["pred_R"], pred_t_pem=out["pred_t"], refine_status=status, refine_rms=rms)
 
 
 def frame_results(det, poses, dataset_name, time_s=0.0):
