@@ -29,7 +29,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from .. import policy
-from ..utils.linear import eligible, fused_linear, lnfold_cached, lnfold_eligible
+from ..utils import fp8, vit_blocks
+from ..utils.linear import eligible, fused_linear, lnfold_eligible
 
 descriptor_size = {"dinov2_vits14": 384, "dinov2_vitb14": 768, "dinov2_vitl14": 1024, "dinov2_vitg14": 1536}
 descriptor_map = {"dinov2_vits14": "vit_small", "dinov2_vitb14": "vit_base", "dinov2_vitl14": "vit_large",
@@ -134,13 +135,48 @@ class Block(nn.Module):
         return c[1:]
 
 
-def _ln_f32(norm):
-    key = (norm.weight._version, norm.bias._version, norm.weight.data_ptr())
-    c = getattr(norm, "_s6d_f32", None)
-    if c is None or c[0] != key:
-        c = (key, norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous())
-        norm._s6d_f32 = c
-    return c[1], c[2]
+class _BlockView(vit_blocks.BlockView):
+    """A Block as the shared block loop sees it (utils/vit_blocks.py): LayerScale already folded into proj / fc2 (Block._folded).
+    x: the (B,N,C) token stream."""
+    fc1 = property(lambda self: self.blk.mlp.fc1)
+
+    def __init__(self, blk, x):
+        super().__init__(blk, x.shape)
+        self.x, self.heads, self.scale = x, blk.attn.num_heads, (x.shape[-1] // blk.attn.num_heads) ** -0.5
+        self.wp, self.bp, self.bpf, self.w2, self.b2, self.b2f = blk._folded(x.dtype)
+
+    def proj(self):
+        return self.wp, self.bpf
+
+    def fc2(self):
+        return self.w2, self.b2f
+
+    def fc2_fp8(self):
+        return DinoVisionTransformer._fc2_fp8(self.blk, self.w2) + (self.b2f,)
+
+    def attention(self, qkv):
+        B, N, C = self.shape
+        return ops.seq_attention(qkv.view(B, N, 3 * C), self.heads, self.scale).reshape(-1, C)
+
+    def _own(self):                                                  # s6d_gemm_bf16 takes both shapes (asked by the delta form only)
+        return eligible(self.x, *self.wp.shape) and eligible(self.x, *self.w2.shape)
+
+    def attn(self, h, residual=None):
+        o = ops.seq_attention(fused_linear(self.blk.attn.qkv, h).contiguous(), self.heads, self.scale)
+        if residual is not None:
+            ops.gemm_bf16(o, self.wp, self.bpf, residual=residual, out=residual.view(-1, self.shape[-1]))
+            return residual
+        return ops.gemm_bf16(o, self.wp, self.bpf) if self._own() else F.linear(o, self.wp, self.bp)
+
+    def mlp(self, h, residual=None):
+        mlp = self.blk.mlp
+        if residual is not None:
+            ops.gemm_bf16(fused_linear(mlp.fc1, h, gelu=True), self.w2, self.b2f, residual=residual,
+                          out=residual.view(-1, self.shape[-1]))
+            return residual
+        if self._own() and isinstance(mlp.act, nn.GELU) and mlp.act.approximate == "none":
+            return ops.gemm_bf16(fused_linear(mlp.fc1, h, gelu=True), self.w2, self.b2f)
+        return F.linear(mlp.act(mlp.fc1(h)), self.w2, self.b2)
 
 
 class DinoVisionTransformer(nn.Module):
@@ -201,121 +237,44 @@ class DinoVisionTransformer(nn.Module):
                             have=ops.have("seq_attention") and ops.have("add_layernorm"))
 
     def _blocks_fused(self, x):
-        """Residual stream through all blocks + the final norm; returns (x_prenorm, x_norm)."""
+        """Residual stream through all blocks + the final norm, through the shared block loop (utils/vit_blocks.py); this method
+        only chooses the form.  Returns (x_prenorm, x_norm)."""
         x = x.contiguous()
-        delta = None
-        scale = (self.embed_dim // self.num_heads) ** -0.5
         C = x.shape[-1]
         exact_gelu = all(isinstance(blk.mlp.act, nn.GELU) and blk.mlp.act.approximate == "none" for blk in self.blocks)
         rows = x.numel() // C
         if policy.current().dino_gemm in ("fp8", "fp8mx"):
-            return self._blocks_fp8(x, scale, exact_gelu)
+            return self._blocks_fp8(x, exact_gelu)
+        views = [_BlockView(blk, x) for blk in self.blocks]
         if (exact_gelu and C % 256 == 0 and all(lnfold_eligible(x, C, C) and lnfold_eligible(x, blk.mlp.fc1.out_features, C) and
                                                 lnfold_eligible(x, C, blk.mlp.fc1.out_features) for blk in self.blocks)
                 and rows <= ops.gemm_one_launch_rows(max(3 * C, max(blk.mlp.fc1.out_features for blk in self.blocks)))):
-            # neither the residual adds nor the block LayerNorms as passes of their own: the same folded loop as the SAM encoder's
-            # (sam/image_encoder.py::_blocks_lnfold), LayerScale already folded into proj / fc2 (Block._folded)
-            x = x.clone()
-            B, N, _ = x.shape
-            x2 = x.view(rows, C)
-            blocks = list(self.blocks)
-            st = ops.row_stats(x2, blocks[0].norm1.eps)
-            sp = torch.empty(C // 32, 2, rows, dtype=torch.float32, device=x.device)
-            for i, blk in enumerate(blocks):
-                wp, bp, bpf, w2, b2, b2f = blk._folded(x.dtype)
-                wf, cs, bf = lnfold_cached(blk.attn.qkv, blk.norm1)
-                qkv = ops.gemm_bf16_lnfold(x2, st, wf, cs, bf).view(B, N, 3 * C)
-                o = ops.seq_attention(qkv, blk.attn.num_heads, scale)
-                ops.gemm_bf16(o.reshape(rows, C), wp, bpf, residual=x2, out=x2, stats_partial=sp)
-                st = ops.ln_stats_finalize(sp, 32, blk.norm2.eps)
-                w1, c1, b1 = lnfold_cached(blk.mlp.fc1, blk.norm2)
-                h = ops.gemm_bf16_lnfold(x2, st, w1, c1, b1, gelu=True)
-                last = i + 1 == len(blocks)
-                ops.gemm_bf16(h, w2, b2f, residual=x2, out=x2, stats_partial=None if last else sp)
-                if not last:
-                    st = ops.ln_stats_finalize(sp, 32, blocks[i + 1].norm1.eps)
-            g, b = _ln_f32(self.norm)
-            return ops.add_layernorm(x, None, g, b, self.norm.eps)
-        if ops.have("gemm_bf16_res") and C % 256 == 0 and exact_gelu and all(
-                eligible(x, C, C) and eligible(x, C, blk.mlp.fc2.in_features) for blk in self.blocks):
-            # round 3: both residual adds of a block in the epilogues of the proj / fc2 GEMMs (in place on the stream tensor),
-            # LayerNorms as one-read passes
-            x = x.clone()
-            M = x.numel() // C
-            for blk in self.blocks:
-                wp, bp, bpf, w2, b2, b2f = blk._folded(x.dtype)
-                g, b = _ln_f32(blk.norm1)
-                _, h = ops.add_layernorm(x, None, g, b, blk.norm1.eps)
-                o = ops.seq_attention(fused_linear(blk.attn.qkv, h).contiguous(), blk.attn.num_heads, scale)
-                ops.gemm_bf16(o, wp, bpf, residual=x, out=x.view(M, C))
-                g, b = _ln_f32(blk.norm2)
-                _, h = ops.add_layernorm(x, None, g, b, blk.norm2.eps)
-                ops.gemm_bf16(fused_linear(blk.mlp.fc1, h, gelu=True), w2, b2f, residual=x, out=x.view(M, C))
-            g, b = _ln_f32(self.norm)
-            return ops.add_layernorm(x, None, g, b, self.norm.eps)
-        for blk in self.blocks:
-            wp, bp, bpf, w2, b2, b2f = blk._folded(x.dtype)
-            own = eligible(x, wp.shape[0], wp.shape[1]) and eligible(x, w2.shape[0], w2.shape[1])   # s6d_gemm_bf16
-            g, b = _ln_f32(blk.norm1)
-            x, h = ops.add_layernorm(x, delta, g, b, blk.norm1.eps)
-            o = ops.seq_attention(fused_linear(blk.attn.qkv, h).contiguous(), blk.attn.num_heads, scale)
-            a = ops.gemm_bf16(o, wp, bpf) if own else F.linear(o, wp, bp)
-            g, b = _ln_f32(blk.norm2)
-            x, h = ops.add_layernorm(x, a, g, b, blk.norm2.eps)
-            if own and isinstance(blk.mlp.act, nn.GELU) and blk.mlp.act.approximate == "none":
-                delta = ops.gemm_bf16(fused_linear(blk.mlp.fc1, h, gelu=True), w2, b2f)
-            else:
-                delta = F.linear(blk.mlp.act(blk.mlp.fc1(h)), w2, b2)
-        g, b = _ln_f32(self.norm)
-        return ops.add_layernorm(x, delta, g, b, self.norm.eps)
+            # neither the residual adds nor the block LayerNorms as passes of their own
+            return vit_blocks.tap(vit_blocks.lnfold(x.clone(), views), None, self.norm)
+        # round 3: both residual adds of a block in the epilogues of the proj / fc2 GEMMs (in place on the stream tensor), LayerNorms
+        # as one-read passes; otherwise every residual add folded into the next LayerNorm pass
+        res = ops.have("gemm_bf16_res") and C % 256 == 0 and exact_gelu and all(
+            eligible(x, C, C) and eligible(x, C, blk.mlp.fc2.in_features) for blk in self.blocks)
+        x, _, (xn,) = vit_blocks.add_layernorm(x.clone() if res else x, views, res, taps=(len(views) - 1,), norm=self.norm)
+        return x, xn
 
-    def _blocks_fp8(self, x, scale, exact_gelu):
+    def _blocks_fp8(self, x, exact_gelu):
         """BASELINE configs[4] for the descriptor ViT (round 4; opt-in: S6D_DINO_GEMM=fp8, never the default): the two LayerNorm-fed
-        GEMMs of every block -- qkv and fc1 + GELU, 58 % of the block's GEMM FLOP -- on the fp8 matrix cores, exactly as the SAM
-        encoder's fp8 loop (sam/image_encoder.py::_blocks_fp8): LayerNorm writes e4m3 rows with one power-of-two scale per token
-        (s6d_layernorm_fp8), the weights carry one per output channel (utils/fp8.py), both ride in the matrix instruction's block
-        scales (s6d_gemm_fp8).  proj and fc2 (LayerScale folded in) stay bf16 with the residual add in their epilogue."""
-        from ..utils import fp8
+        GEMMs of every block -- qkv and fc1 + GELU, 58 % of the block's GEMM FLOP -- on the fp8 matrix cores (utils/vit_blocks.py::
+        fp8).  proj and fc2 (LayerScale folded in) stay bf16 with the residual add in their epilogue.  S6D_DINO_GEMM=fp8mx: fc2 too,
+        fed by fc1's MX-scaled e4m3 output; fc2's bf16 output is the delta the next quantising LayerNorm, or the final norm, adds."""
         C = x.shape[-1]
         if not (exact_gelu and ops.have("gemm_fp8") and ops.have("layernorm_fp8") and ops.have("gemm_bf16_res") and x.is_cuda
                 and x.dtype == torch.bfloat16 and C % 256 == 0 and C <= 2048):
             raise RuntimeError("S6D_DINO_GEMM=fp8 needs the fp8 kernels of libsam6d_hip.so, a bf16 device token stream, exact GELU "
                                "and 256 | C <= 2048")
-        x = x.clone()
-        B, N, _ = x.shape
-        rows = B * N
-        x2 = x.view(rows, C)
-        # S6D_DINO_GEMM=fp8mx: fc2 too, fed by fc1's MX-scaled e4m3 output (s6d_gemm_fp8_gelu_mx -> s6d_gemm_fp8_mxa, as the SAM
-        # encoder's fp8mx loop); fc2's bf16 output is the delta the next quantising LayerNorm adds
         mx = policy.current().dino_gemm == "fp8mx" and ops.have("gemm_fp8_mx")
-        delta = None
-        for blk in self.blocks:
-            wp, bp, bpf, w2, b2, b2f = blk._folded(x.dtype)
-            g, b = _ln_f32(blk.norm1)
-            if delta is None:
-                h8, hs = ops.layernorm_fp8(x2, g, b, blk.norm1.eps)
-            else:
-                x2, h8, hs = ops.layernorm_fp8(x2, g, b, blk.norm1.eps, delta=delta)
-            wq, ws, bq = fp8.cached_weight(blk.attn.qkv)
-            qkv = ops.gemm_fp8(h8, hs, wq, ws, bq).view(B, N, 3 * C)
-            o = ops.seq_attention(qkv, blk.attn.num_heads, scale)
-            ops.gemm_bf16(o.reshape(rows, C), wp, bpf, residual=x2, out=x2)
-            g, b = _ln_f32(blk.norm2)
-            h8, hs = ops.layernorm_fp8(x2, g, b, blk.norm2.eps)
-            w1, s1, b1 = fp8.cached_weight(blk.mlp.fc1)
-            if mx:
-                q8, qs = ops.gemm_fp8_gelu_mx(h8, hs, w1, s1, b1)
-                w2q, w2s = self._fc2_fp8(blk, w2)
-                delta = ops.gemm_fp8_mxa(q8, qs, w2q, w2s, b2f)
-            else:
-                ops.gemm_bf16(ops.gemm_fp8(h8, hs, w1, s1, b1, gelu=True), w2, b2f, residual=x2, out=x2)
-        g, b = _ln_f32(self.norm)
-        return ops.add_layernorm(x2.view(B, N, C), None if delta is None else delta.view(B, N, C), g, b, self.norm.eps)
+        x2, delta = vit_blocks.fp8(x.clone().view(-1, C), [_BlockView(blk, x) for blk in self.blocks], mx, True)
+        return vit_blocks.tap(x2.view(x.shape), None if delta is None else delta.view(x.shape), self.norm)
 
     @staticmethod
     def _fc2_fp8(blk, w2_folded):
         """e4m3 bytes + per-channel scales of fc2 with the LayerScale gain folded in (Block._folded), cached on the folded tensor."""
-        from ..utils import fp8
         c = getattr(blk, "_s6d_fc2_fp8", None)
         key = (w2_folded.data_ptr(), w2_folded._version)
         if c is None or c[0] != key:

@@ -20,7 +20,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from .. import policy
-from ..utils.linear import fused_linear
+from ..utils import vit_blocks
+from ..utils.linear import fused_linear, res_eligible
 
 
 _FORCE_DTYPE = []     # non-empty: the innermost entry overrides S6D_PEM_VIT_DTYPE (the fp32 re-run of the range guard)
@@ -91,6 +92,18 @@ class _PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(3, dim, kernel_size=patch, stride=patch)
 
 
+class _BlockView(vit_blocks.BlockView):
+    """A _Block as the shared block loop sees it (utils/vit_blocks.py): the two branches, in the add + LayerNorm forms."""
+
+    def attn(self, h, residual=None):
+        at = self.blk.attn
+        o = ops.seq_attention(fused_linear(at.qkv, h).contiguous(), at.num_heads, (self.shape[-1] // at.num_heads) ** -0.5)
+        return fused_linear(at.proj, o, residual=residual)
+
+    def mlp(self, h, residual=None):
+        return fused_linear(self.blk.mlp.fc2, fused_linear(self.blk.mlp.fc1, h, gelu=True), residual=residual)
+
+
 class ViT(nn.Module):
     """feature_extraction.py:17-35: returns norm(x) after blocks d-3n-1, d-2n-1, d-n-1, d-1."""
 
@@ -129,59 +142,17 @@ class ViT(nn.Module):
                 out.append(self.norm(x))
         return out
 
-
-def _ln_f32(norm):
-    key = (norm.weight._version, norm.bias._version, norm.weight.data_ptr())
-    c = getattr(norm, "_s6d_f32", None)
-    if c is None or c[0] != key:
-        c = (key, norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous())
-        norm._s6d_f32 = c
-    return c[1], c[2]
-
-
-def _vit_forward_fused(self, x, taps):
-    """bf16 pipeline on the gfx950 kernels: every residual add is folded into the next LayerNorm pass
-    (s6d_add_layernorm_bf16), attention runs in the fused MFMA kernel (s6d_seq_attention_bf16); the four
-    library GEMMs per block stay library GEMMs.  A tap is norm(x_i) of the residual stream after block i."""
-    x = x.contiguous()
-    delta = None
-    out = []
-    from ..utils.linear import res_eligible
-    C = x.shape[-1]
-    if all(res_eligible(x, C, C) and res_eligible(x, C, blk.mlp.fc2.in_features) for blk in self.blocks):
-        # round 3: residual adds in the epilogues of the proj / fc2 GEMMs (in place), LayerNorms as one-read passes
-        x = x.clone()
-        scale = (C // self.blocks[0].attn.num_heads) ** -0.5
-        for i, blk in enumerate(self.blocks):
-            g, b = _ln_f32(blk.norm1)
-            _, h = ops.add_layernorm(x, None, g, b, blk.norm1.eps)
-            o = ops.seq_attention(fused_linear(blk.attn.qkv, h).contiguous(), blk.attn.num_heads, scale)
-            x = fused_linear(blk.attn.proj, o, residual=x)
-            g, b = _ln_f32(blk.norm2)
-            _, h = ops.add_layernorm(x, None, g, b, blk.norm2.eps)
-            x = fused_linear(blk.mlp.fc2, fused_linear(blk.mlp.fc1, h, gelu=True), residual=x)
-            if i in taps:
-                g, b = _ln_f32(self.norm)
-                out.append(ops.add_layernorm(x, None, g, b, self.norm.eps)[1])
-        return out
-    for i, blk in enumerate(self.blocks):
-        g, b = _ln_f32(blk.norm1)
-        x, h = ops.add_layernorm(x, delta, g, b, blk.norm1.eps)
-        qkv = fused_linear(blk.attn.qkv, h)
-        a = fused_linear(blk.attn.proj,
-                         ops.seq_attention(qkv.contiguous(), blk.attn.num_heads, (x.shape[-1] // blk.attn.num_heads) ** -0.5))
-        g, b = _ln_f32(blk.norm2)
-        x, h = ops.add_layernorm(x, a.contiguous(), g, b, blk.norm2.eps)
-        delta = blk.mlp(h).contiguous()
-        if i in taps:
-            g, b = _ln_f32(self.norm)
-            x, t = ops.add_layernorm(x, delta, g, b, self.norm.eps)
-            delta = None
-            out.append(t)
-    return out
-
-
-ViT._forward_fused = _vit_forward_fused
+    def _forward_fused(self, x, taps):
+        """Half-precision pipeline on the gfx950 kernels, through the shared block loop (utils/vit_blocks.py): attention in the
+        fused MFMA kernel (s6d_seq_attention_*), the four Linear layers of a block through fused_linear.  S6D_GEMM_RES=1 on a bf16
+        stream (round 3): residual adds in the epilogues of the proj / fc2 GEMMs (in place), LayerNorms as one-read passes;
+        otherwise every residual add is folded into the next LayerNorm pass (s6d_add_layernorm_*).  A tap is norm(x_i) of the
+        residual stream after block i."""
+        x = x.contiguous()
+        C = x.shape[-1]
+        res = all(res_eligible(x, C, C) and res_eligible(x, C, blk.mlp.fc2.in_features) for blk in self.blocks)
+        views = [_BlockView(blk, x.shape) for blk in self.blocks]
+        return vit_blocks.add_layernorm(x.clone() if res else x, views, res, taps, self.norm)[2]
 
 
 class ViT_AE(nn.Module):

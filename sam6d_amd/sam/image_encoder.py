@@ -15,7 +15,6 @@ Hardware-first execution:
   * decomposed relative position bias is added inside the attention kernel from per-query tables
     (never a (heads,4096,4096) tensor).
 """
-import os
 from typing import Optional, Tuple, Type
 
 import torch
@@ -24,7 +23,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from .. import policy
-from ..utils.linear import fused_linear
+from ..utils import fp8, vit_blocks
+from ..utils.linear import cached_operands, fused_linear, lnfold_eligible, res_eligible
 
 
 def _dtype():
@@ -124,16 +124,19 @@ class Attention(nn.Module):
             self._s6d_attn_ops = c
         return c[1], c[2], c[3]
 
+    def _window_attention(self, qkv, window_size, head_major_shape=None):
+        """The fused attention kernel on the (B,H,W,3C) projection (or its head-major form) with this module's cached operands."""
+        S = window_size if window_size > 0 else (head_major_shape or qkv.shape)[1]
+        bias, rh, rw = self._kernel_operands(S, qkv.dtype)
+        return ops.window_attention(qkv, bias, rh, rw, self.num_heads, window_size, self.scale, head_major_shape=head_major_shape)
+
     def forward(self, x, window_size=0, residual=None, qkv=None):
         """x: (B,H,W,C) token map (already normed).  window_size 0 = global attention.  residual: the block's shortcut -- the
         result is then shortcut + attention, with the add in the proj GEMM's epilogue (written over `residual`).  qkv: the
         (B,H,W,3C) projection when the caller has made it already (fp8 path: x is then only consulted for its shape)."""
         B, H, W, C = x.shape
         if qkv is not None:
-            S = window_size if window_size > 0 else H
-            bias, rh, rw = self._kernel_operands(S, qkv.dtype)
-            out = ops.window_attention(qkv.contiguous(), bias, rh, rw, self.num_heads, window_size, self.scale)
-            return fused_linear(self.proj, out, residual=residual)
+            return fused_linear(self.proj, self._window_attention(qkv.contiguous(), window_size), residual=residual)
         fused = policy.guard("sam.Attention", cuda=x.is_cuda, have=ops.have("win_attention"), bf16=x.dtype == torch.bfloat16, rel_pos=self.use_rel_pos)
         if fused:
             # S6D_QKV_LAYOUT=head: q / k / v head-major straight out of the GEMM's epilogue ((3 heads, B H W, hd): a head's rows of a
@@ -141,15 +144,10 @@ class Attention(nn.Module):
             # step, so the default stays the Linear layout (fused_linear returns None)
             hm = fused_linear(self.qkv, x, col_block=C // self.num_heads)
             if hm is not None:
-                S = window_size if window_size > 0 else H
-                bias, rh, rw = self._kernel_operands(S, hm.dtype)
-                out = ops.window_attention(hm, bias, rh, rw, self.num_heads, window_size, self.scale, head_major_shape=(B, H, W))
-                return fused_linear(self.proj, out, residual=residual)
+                return fused_linear(self.proj, self._window_attention(hm, window_size, (B, H, W)), residual=residual)
         qkv = fused_linear(self.qkv, x)                              # (B,H,W,3C): real tokens only
         if fused:
-            S = window_size if window_size > 0 else H
-            bias, rh, rw = self._kernel_operands(S, qkv.dtype)
-            out = ops.window_attention(qkv.contiguous(), bias, rh, rw, self.num_heads, window_size, self.scale)
+            out = self._window_attention(qkv.contiguous(), window_size)
         else:
             out = self._attention_lib(qkv, B, H, W, C, window_size)
         return fused_linear(self.proj, out, residual=residual)
@@ -203,6 +201,35 @@ class Block(nn.Module):
         return x + self.mlp(self.norm2(x))
 
 
+class _BlockView(vit_blocks.BlockView):
+    """A Block as the shared block loop sees it (utils/vit_blocks.py); `shape`: the (B,H,W,C) of the token map."""
+    fc1 = property(lambda self: self.blk.mlp.lin1)
+
+    def proj(self):
+        return cached_operands(self.blk.attn.proj, self.blk.attn.proj.weight)
+
+    def fc2(self):
+        return cached_operands(self.blk.mlp.lin2, self.blk.mlp.lin2.weight)
+
+    def fc2_fp8(self):
+        return fp8.cached_weight(self.blk.mlp.lin2)
+
+    def attention(self, qkv):
+        B, H, W, C = self.shape
+        return self.blk.attn._window_attention(qkv.view(B, H, W, 3 * C), self.blk.window_size).reshape(-1, C)
+
+    # the module's own statements: S6D_QKV_LAYOUT=head, _attention_lib and the library GEMM stay reachable through them
+    def attn(self, h, residual=None, qkv=None):
+        return self.blk.attn(h, self.blk.window_size, residual=residual, qkv=qkv)
+
+    def mlp(self, h, residual=None):
+        mlp = self.blk.mlp
+        return mlp(h) if residual is None else fused_linear(mlp.lin2, fused_linear(mlp.lin1, h, gelu=True), residual=residual)
+
+    def fc2_linear(self, h):
+        return fused_linear(self.blk.mlp.lin2, h)
+
+
 class ImageEncoderViT(nn.Module):
     def __init__(self, img_size: int = 1024, patch_size: int = 16, in_chans: int = 3, embed_dim: int = 768,
                  depth: int = 12, num_heads: int = 12, mlp_ratio: float = 4.0, out_chans: int = 256,
@@ -240,167 +267,47 @@ class ImageEncoderViT(nn.Module):
             x = blk(x)
         return x
 
-    @staticmethod
-    def _ln_f32(norm):
-        """fp32 copies of a LayerNorm's affine parameters, cached until the parameters change."""
-        key = (norm.weight._version, norm.bias._version, norm.weight.data_ptr())
-        c = getattr(norm, "_s6d_f32", None)
-        if c is None or c[0] != key:
-            c = (key, norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous())
-            norm._s6d_f32 = c
-        return c[1], c[2]
+    def _views(self, x, upto):
+        return [_BlockView(blk, x.shape) for blk in list(self.blocks)[:upto]]
 
     def _blocks_fused(self, x, upto, own=False):
-        """Same dataflow as Block.forward.  Round 3: the two residual adds of a block happen in the epilogues of the proj and
-        lin2 GEMMs (s6d_gemm_bf16_res, in place on the stream tensor) and the LayerNorms are one-read passes; round 2 folded
-        each add into the following LayerNorm pass (two reads + two writes per add: 6 % of the step).  Same arithmetic either
-        way (the add rounds the GEMM's bf16 output + x to bf16): S6D_DISABLE_FUSED=gemm_bf16_res selects the round-2 form."""
-        from ..utils.linear import lnfold_eligible, res_eligible
+        """Same dataflow as Block.forward, through the shared block loop (utils/vit_blocks.py); this method only chooses the form.
+        Default: residual adds and LayerNorms folded into the GEMMs (lnfold).  S6D_LNFOLD=0 S6D_GEMM_RES=1 (round 3): the two
+        residual adds of a block in the epilogues of the proj and lin2 GEMMs (in place on the stream tensor), LayerNorms as one-read
+        passes; otherwise round 2: each add folded into the following LayerNorm pass.  Same arithmetic either way (the add rounds
+        the GEMM's bf16 output + x to bf16).  Out-of-image window tokens keep the ORIGINAL qkv bias in every form (the reference
+        pads after norm1: zeros through qkv = its bias).  own: x is the caller's to give away (no clone before in-place updates)."""
         x = x.contiguous()
         C = x.shape[-1]
         if _gemm_mode() in ("fp8", "fp8mx"):
             return self._blocks_fp8(x, upto, own)
         rows, hid = x.numel() // C, max(blk.mlp.lin1.out_features for blk in self.blocks)
+        views = self._views(x, upto)
         if policy.guard("sam.ImageEncoderViT.lnfold", cuda=x.is_cuda,
                         eligible=lnfold_eligible(x, C, C) and C % 32 == 0 and all(
                             lnfold_eligible(x, blk.mlp.lin1.out_features, C) and lnfold_eligible(x, C, blk.mlp.lin1.out_features)
                             and blk.attn.use_rel_pos for blk in self.blocks),
                         have=ops.have("win_attention"), one_launch_rows=rows <= ops.gemm_one_launch_rows(max(hid, 3 * C))):
-            return self._blocks_lnfold(x, upto, own)
-        if res_eligible(x, C, C) and all(res_eligible(x, C, blk.mlp.lin2.in_features) for blk in self.blocks):
-            x = x.clone()                                        # the stream tensor is updated in place from here on
-            for i, blk in enumerate(self.blocks):
-                if upto is not None and i >= upto:
-                    break
-                g, b = self._ln_f32(blk.norm1)
-                _, h = ops.add_layernorm(x, None, g, b, blk.norm1.eps)
-                x = blk.attn(h, blk.window_size, residual=x)
-                g, b = self._ln_f32(blk.norm2)
-                _, h = ops.add_layernorm(x, None, g, b, blk.norm2.eps)
-                x = fused_linear(blk.mlp.lin2, fused_linear(blk.mlp.lin1, h, gelu=True), residual=x)
-            return x
-        delta = None
-        for i, blk in enumerate(self.blocks):
-            if upto is not None and i >= upto:
-                break
-            g, b = self._ln_f32(blk.norm1)
-            x, h = ops.add_layernorm(x, delta, g, b, blk.norm1.eps)
-            a = blk.attn(h, blk.window_size)
-            g, b = self._ln_f32(blk.norm2)
-            x, h = ops.add_layernorm(x, a.contiguous(), g, b, blk.norm2.eps)
-            delta = blk.mlp(h).contiguous()
+            return vit_blocks.lnfold(x if own else x.clone(), views)
+        res = res_eligible(x, C, C) and all(res_eligible(x, C, blk.mlp.lin2.in_features) for blk in self.blocks)
+        x, delta, _ = vit_blocks.add_layernorm(x.clone() if res else x, views, res)
         return x if delta is None else x + delta
-
-    def _blocks_lnfold(self, x, upto, own=False):
-        """Block.forward (image_encoder.py:166-182) with neither the residual adds nor the LayerNorms as passes of their own
-        (round 2 / 3 spent 6 % of the step in add + LayerNorm: two reads and two writes of the token map per add):
-          * `x + proj(..)` and `x + lin2(..)`: the residual tile rides through the matrix cores of the producing GEMM
-            (s6d_gemm_bf16_res, in place on the stream tensor), whose epilogue also leaves per-row partial statistics of the new x;
-          * `norm1(x)` / `norm2(x)`: s6d_ln_stats_finalize turns the partials into (mean, sigma) per token (a 20-MB pass), and the
-            consuming GEMM (qkv, lin1 + GELU) multiplies the RAW stream by gamma * W, starting its accumulators at
-            sigma b' - mean s and dividing by sigma in its epilogue (s6d_gemm_bf16_lnfold).  The normalised activations never exist.
-        Out-of-image window tokens keep the ORIGINAL qkv bias (the reference pads after norm1: zeros through qkv = its bias)."""
-        from ..utils.linear import _cached, lnfold_cached
-        if not own:
-            x = x.clone()                                        # the stream tensor is updated in place from here on
-        B, H, W, C = x.shape
-        M = B * H * W
-        x2 = x.view(M, C)
-        blocks = list(self.blocks)[:upto] if upto is not None else list(self.blocks)
-        if not blocks:
-            return x
-        st = ops.row_stats(x2, blocks[0].norm1.eps)
-        sp = torch.empty(C // 32, 2, M, dtype=torch.float32, device=x.device)
-        for i, blk in enumerate(blocks):
-            at = blk.attn
-            wf, cs, bf = lnfold_cached(at.qkv, blk.norm1)
-            qkv = ops.gemm_bf16_lnfold(x2, st, wf, cs, bf).view(B, H, W, 3 * C)
-            S = blk.window_size if blk.window_size > 0 else H
-            bias, rh, rw = at._kernel_operands(S, qkv.dtype)
-            a = ops.window_attention(qkv, bias, rh, rw, at.num_heads, blk.window_size, at.scale)
-            wp, bp = _cached(at.proj, at.proj.weight)
-            ops.gemm_bf16(a.reshape(M, C), wp, bp, residual=x2, out=x2, stats_partial=sp)
-            st = ops.ln_stats_finalize(sp, 32, blk.norm2.eps)
-            w1, c1, b1 = lnfold_cached(blk.mlp.lin1, blk.norm2)
-            h = ops.gemm_bf16_lnfold(x2, st, w1, c1, b1, gelu=True)
-            w2, b2 = _cached(blk.mlp.lin2, blk.mlp.lin2.weight)
-            last = i + 1 == len(blocks)
-            ops.gemm_bf16(h, w2, b2, residual=x2, out=x2, stats_partial=None if last else sp)
-            if not last:
-                st = ops.ln_stats_finalize(sp, 32, blocks[i + 1].norm1.eps)
-        return x
 
     def _blocks_fp8(self, x, upto, own=False):
         """BASELINE configs[4] (never the headline): the two LayerNorm-fed GEMMs of every block -- qkv (1280 -> 3840) and lin1
-        (1280 -> 5120, + GELU), 58 % of the encoder's GEMM FLOP -- on the fp8 matrix cores.  LayerNorm writes its output as e4m3
-        bytes with one power-of-two scale per token (s6d_layernorm_fp8: no extra pass), the weights carry one power-of-two scale
-        per output channel (utils/fp8.py), both ride in the matrix instruction's block-scale operands (s6d_gemm_fp8).  proj and
+        (1280 -> 5120, + GELU), 58 % of the encoder's GEMM FLOP -- on the fp8 matrix cores (utils/vit_blocks.py::fp8).  proj and
         lin2 (their inputs come out of the attention kernel / the GELU epilogue in bf16, and a per-token scale needs the whole
-        row) stay bf16, as do attention, the residual stream and the neck."""
-        from ..utils import fp8
+        row) stay bf16, as do attention, the residual stream and the neck.  S6D_SAM_GEMM=fp8mx (round 4): lin2 on them too."""
         C = x.shape[-1]
         if not (ops.have("gemm_fp8") and ops.have("layernorm_fp8") and x.is_cuda and x.dtype == torch.bfloat16 and C % 256 == 0):
             raise RuntimeError("S6D_SAM_GEMM=fp8 needs the fp8 kernels of libsam6d_hip.so, a bf16 device token map and C % 256 == 0")
-        from ..utils.linear import _cached
-        B, H, W, _ = x.shape
-        M = B * H * W
-        if ops.have("gemm_bf16_res") and all(blk.attn.use_rel_pos for blk in self.blocks) and ops.have("win_attention") \
-                and M <= ops.gemm_one_launch_rows(max(blk.mlp.lin1.out_features for blk in self.blocks)):
-            # the residual adds in the bf16 proj / lin2 GEMMs (accumulators start at bias + residual, in place on the stream
-            # tensor): the quantising LayerNorm then reads ONE tensor and writes its e4m3 rows
-            if not own:
-                x = x.clone()
-            x2 = x.view(M, C)
-            mx = _gemm_mode() == "fp8mx" and ops.have("gemm_fp8_mx") and M % 256 == 0
-            delta = None
-            for i, blk in enumerate(self.blocks):
-                if upto is not None and i >= upto:
-                    break
-                at = blk.attn
-                g, b = self._ln_f32(blk.norm1)
-                if delta is None:
-                    h8, hs = ops.layernorm_fp8(x, g, b, blk.norm1.eps)
-                else:                                              # fp8mx: the previous block's lin2 output joins the stream here
-                    x, h8, hs = ops.layernorm_fp8(x, g, b, blk.norm1.eps, delta=delta)
-                    x2 = x.view(M, C)
-                wq, ws, bq = fp8.cached_weight(at.qkv)
-                qkv = ops.gemm_fp8(h8, hs, wq, ws, bq).view(B, H, W, 3 * C)
-                S = blk.window_size if blk.window_size > 0 else H
-                bias, rh, rw = at._kernel_operands(S, qkv.dtype)
-                a = ops.window_attention(qkv, bias, rh, rw, at.num_heads, blk.window_size, at.scale)
-                wp, bp = _cached(at.proj, at.proj.weight)
-                ops.gemm_bf16(a.reshape(M, C), wp, bp, residual=x2, out=x2)
-                g, b = self._ln_f32(blk.norm2)
-                h8, hs = ops.layernorm_fp8(x, g, b, blk.norm2.eps)
-                w1, s1, b1 = fp8.cached_weight(blk.mlp.lin1)
-                if mx:
-                    # S6D_SAM_GEMM=fp8mx (round 4): lin1's GELU epilogue writes e4m3 with MX block scales (one E8M0 byte per token
-                    # and 32 channels), lin2 multiplies them on the fp8 matrix cores -- the 5120-wide hidden activations never exist
-                    # in bf16.  lin2's output is a bf16 delta that the next quantising LayerNorm adds to the stream
-                    # (s6d_add_layernorm_fp8): the fp8 kernel has no registers left for the residual epilogue.
-                    q8, qs = ops.gemm_fp8_gelu_mx(h8, hs, w1, s1, b1)
-                    w2q, w2s, b2f = fp8.cached_weight(blk.mlp.lin2)
-                    delta = ops.gemm_fp8_mxa(q8, qs, w2q, w2s, b2f).view(x.shape)
-                else:
-                    w2, b2 = _cached(blk.mlp.lin2, blk.mlp.lin2.weight)
-                    ops.gemm_bf16(ops.gemm_fp8(h8, hs, w1, s1, b1, gelu=True), w2, b2, residual=x2, out=x2)
-            return x if delta is None else x + delta
-        delta = None
-        for i, blk in enumerate(self.blocks):
-            if upto is not None and i >= upto:
-                break
-            # each residual add folded into the following quantising LayerNorm pass, as in the round-2 bf16 loop
-            g, b = self._ln_f32(blk.norm1)
-            if delta is None:
-                h8, hs = ops.layernorm_fp8(x, g, b, blk.norm1.eps)
-            else:
-                x, h8, hs = ops.layernorm_fp8(x, g, b, blk.norm1.eps, delta=delta)
-            wq, ws, bq = fp8.cached_weight(blk.attn.qkv)
-            a = blk.attn(x, blk.window_size, qkv=ops.gemm_fp8(h8, hs, wq, ws, bq))
-            g, b = self._ln_f32(blk.norm2)
-            x, h8, hs = ops.layernorm_fp8(x, g, b, blk.norm2.eps, delta=a.contiguous())
-            w1, s1, b1 = fp8.cached_weight(blk.mlp.lin1)
-            delta = fused_linear(blk.mlp.lin2, ops.gemm_fp8(h8, hs, w1, s1, b1, gelu=True)).contiguous()
+        M = x.numel() // C
+        # with the residual adds in the bf16 proj / lin2 GEMMs when those kernels take the shapes, otherwise each add folded into
+        # the following quantising LayerNorm pass, as in the round-2 bf16 loop
+        res = ops.have("gemm_bf16_res") and all(blk.attn.use_rel_pos for blk in self.blocks) and ops.have("win_attention") \
+            and M <= ops.gemm_one_launch_rows(max(blk.mlp.lin1.out_features for blk in self.blocks))
+        mx = res and _gemm_mode() == "fp8mx" and ops.have("gemm_fp8_mx") and M % 256 == 0
+        x, delta = vit_blocks.fp8(x.clone() if res and not own else x, self._views(x, upto), mx, res)
         return x if delta is None else x + delta
 
     def neck_nhwc(self, t):
@@ -414,7 +321,7 @@ class ImageEncoderViT(nn.Module):
         kern = policy.guard("sam.neck.LayerNorm2d", cuda=y.is_cuda, bf16=dt == torch.bfloat16,
                             have=ops.have("add_layernorm") and ops.have("layernorm_f32out"), C8=y.shape[-1] % 8 == 0)
         if kern:                                                            # LayerNorm2d = LN over the channel (last) dim: one kernel pass
-            g, b = self._ln_f32(n1)
+            g, b = vit_blocks.ln_f32(n1)
             y = ops.add_layernorm(y.contiguous(), None, g, b, n1.eps)[1]
         else:
             y = F.layer_norm(y.float(), (y.shape[-1],), n1.weight.float(), n1.bias.float(), n1.eps).to(dt)
@@ -430,7 +337,7 @@ class ImageEncoderViT(nn.Module):
                 cols = torch.cat([yp[:, dy:dy + H, dx:dx + W, :] for dy in range(3) for dx in range(3)], dim=-1)
             acc = fused_linear(c3, cols, weight2d=c3.weight.permute(0, 2, 3, 1).reshape(c3.weight.shape[0], -1))
             if kern:                                                        # bf16 GEMM output -> fp32 embedding, statistics in fp32
-                g, b = self._ln_f32(n2)
+                g, b = vit_blocks.ln_f32(n2)
                 return ops.layernorm_f32out(acc.contiguous(), g, b, n2.eps).permute(0, 3, 1, 2)
             acc = acc.float()
         else:

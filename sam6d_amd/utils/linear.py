@@ -5,8 +5,6 @@ how the statement  act(x @ W^T + b)  is executed: on a device bf16 activation wi
 launch of s6d_gemm_bf16 (bias and GELU in the epilogue; `residual=`: the block's residual add in the epilogue too), otherwise
 the library statement.  `S6D_DISABLE_FUSED=gemm_bf16`
 turns the kernel off (A/B runs)."""
-import os
-
 import torch
 import torch.nn.functional as F
 
@@ -14,7 +12,7 @@ from .. import ops
 from .. import policy
 
 
-def _cached(lin, w2d, dtype=torch.bfloat16):
+def cached_operands(lin, w2d, dtype=torch.bfloat16):
     """bf16 (or float16) weight (N,K) + fp32 bias of a Linear / 1x1-or-patch Conv, cached until the parameters change."""
     b = lin.bias
     key = (lin.weight._version, lin.weight.data_ptr(), lin.weight.dtype, None if b is None else (b._version, b.data_ptr()), dtype)
@@ -25,6 +23,9 @@ def _cached(lin, w2d, dtype=torch.bfloat16):
         c = (key, wb, bf)
         lin._s6d_gemm = c
     return c[1], c[2]
+
+
+_cached = cached_operands     # the name this had while it was private to this module
 
 
 class CastCachedLinear(torch.nn.Linear):
@@ -109,18 +110,18 @@ def fused_linear(lin, x, gelu=False, weight2d=None, col_block=0, residual=None):
     N, K = w.shape
     if col_block:
         if eligible(x, N, K) and N % 256 == 0 and policy.current().qkv_layout == "head":
-            wb, bf = _cached(lin, w)
+            wb, bf = cached_operands(lin, w)
             return ops.gemm_bf16(x, wb, bf, gelu=gelu, col_block=col_block)
         return None
     if residual is not None:
         # residual + lin(x): in the GEMM's epilogue when the kernel takes the shape, written over the residual (the caller's
         # stream tensor: nothing else holds it), otherwise the two statements
         if res_eligible(x, N, K) and residual.dtype == torch.bfloat16 and residual.is_contiguous():
-            wb, bf = _cached(lin, w)
+            wb, bf = cached_operands(lin, w)
             return ops.gemm_bf16(x, wb, bf, residual=residual, out=residual.reshape(-1, N)).reshape(residual.shape)
         return residual + fused_linear(lin, x, gelu=gelu, weight2d=weight2d)
     if eligible(x, N, K):
-        wb, bf = _cached(lin, w, x.dtype)
+        wb, bf = cached_operands(lin, w, x.dtype)
         return ops.gemm_bf16(x, wb, bf, gelu=gelu)
     # the library statement (rocBLAS / hipBLASLt on the device): recorded, and an error under strict mode (sam6d_amd/policy.py)
     policy.guard("utils.fused_linear", cuda=x.is_cuda, half_dtype=x.dtype in (torch.bfloat16, torch.float16),
