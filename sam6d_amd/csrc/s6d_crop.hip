@@ -9,6 +9,8 @@
 // kernel mirrors ATen's nearest index rule (UpSample.h nearest_neighbor_compute_source_index, the one the CUDA kernel
 // and the CPU generic kernel use): src = min(floorf(dst * float(1 / scale)), in - 1) with the USER scale_factor, not
 // out / in -- also when out == in (a 17-wide crop "resized" by 1.04 to 17 columns repeats column 0 and drops 16).
+// That geometry (crop_src) and the three-plane store are s6d_crop_params.h's, shared with the template crops of s6d_onboard.hip,
+// which differ in the pixel arithmetic alone; a record whose source pixel lies outside the frame gives padding (rgb 0, mask 0).
 #include "s6d_common.h"
 #include "s6d_crop_params.h"
 
@@ -23,16 +25,9 @@ __global__ __launch_bounds__(256) void crop_resize_pad_kernel(const unsigned cha
   const int p = blockIdx.y;
   const int o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= T * T) return;
-  const CropParams c = params[p];
-  const int oy = o / T, ox = o - oy * T;
-  // second resize: padded square (S2) -> T
-  const int py = nearest_src(oy, c.S2, c.inv2), px = nearest_src(ox, c.S2, c.inv2);
-  // padding
-  const int iy = py - c.top, ix = px - c.left;
+  int sy, sx;
   float r = 0.f, g = 0.f, b = 0.f, mk = 0.f;
-  if (iy >= 0 && iy < c.h1 && ix >= 0 && ix < c.w1) {
-    // first resize: crop (h, w) -> (h1, w1)
-    const int sy = c.y1 + nearest_src(iy, c.h, c.inv1), sx = c.x1 + nearest_src(ix, c.w, c.inv1);
+  if (crop_src(params[p], o, T, H, W, sy, sx)) {
     const size_t pix = (size_t)sy * W + sx;
     mk = masks[(size_t)p * H * W + pix];
     if (out_rgb) {
@@ -43,14 +38,8 @@ __global__ __launch_bounds__(256) void crop_resize_pad_kernel(const unsigned cha
       b = (((float)q[2] / 255.0f - m2) / s2) * mk;
     }
   }
-  const size_t plane = (size_t)T * T;
-  if (out_rgb) {
-    float *d = out_rgb + (size_t)p * 3 * plane + o;
-    d[0] = r;
-    d[plane] = g;
-    d[2 * plane] = b;
-  }
-  if (out_mask) out_mask[(size_t)p * plane + o] = mk;
+  if (out_rgb) store_rgb_planes(out_rgb + (size_t)p * 3 * T * T, o, T, r, g, b);
+  if (out_mask) out_mask[(size_t)p * T * T + o] = mk;
 }
 
 }  // namespace s6d
@@ -60,11 +49,10 @@ using namespace s6d;
 extern "C" int s6d_crop_resize_pad_f32(const unsigned char *image, const float *masks, const void *params, int P, int H,
                                        int W, int T, const float *mean3_host, const float *std3_host, float *out_rgb,
                                        float *out_mask, void *stream) {
-  if (P < 0 || H <= 0 || W <= 0 || T <= 0) return S6D_EINVAL;
+  if (P < 0 || H <= 0 || W <= 0 || T <= 0 || (long)H * W > 0x7fffffffL) return S6D_EINVAL;
   if (P == 0) return S6D_OK;
   if (!masks || !params || (!out_rgb && !out_mask) || (out_rgb && (!image || !mean3_host || !std3_host)))
     return S6D_EINVAL;
-  static_assert(sizeof(CropParams) == 48, "CropParams is the 12-int record of include/sam6d_hip.h");
   const float one[3] = {1.f, 1.f, 1.f}, zero[3] = {0.f, 0.f, 0.f};
   const float *m = out_rgb ? mean3_host : zero, *s = out_rgb ? std3_host : one;
   const dim3 grid((unsigned)((T * T + 255) / 256), (unsigned)P);

@@ -1,6 +1,6 @@
-// Geometry record of CropResizePad.__call__ (Instance_Segmentation_Model/utils/bbox_utils.py:98-126) and ATen's nearest index rule:
-// shared by the proposal crops (s6d_crop.hip) and the template crops of the onboarding (s6d_onboard.hip).  The host side
-// (sam6d_amd/ism/dinov2.py crop_params) fills one record per crop.
+// Geometry of CropResizePad.__call__ (Instance_Segmentation_Model/utils/bbox_utils.py:98-126) with ATen's nearest index rule, and the
+// reference's square crop box: shared by the proposal crops (s6d_crop.hip), the template crops of the onboarding (s6d_onboard.hip)
+// and the mask boxes of both (s6d_compact.h).  The host side (sam6d_amd/ism/dinov2.py crop_params) fills one record per crop.
 #pragma once
 #include "s6d_common.h"
 
@@ -18,6 +18,27 @@ struct CropParams {     // 12 x 4 bytes; all sizes in pixels
 
 __device__ __forceinline__ int nearest_src(int dst, int in, float inv) {
   return min((int)floorf((float)dst * inv), in - 1);
+}
+
+// Output pixel o of the S x S crop of record c -> its source pixel (sy, sx) in the H x W frame: the second resize (padded square -> S),
+// the padding, the first resize (crop -> h1 x w1).  false = padding; a source outside the frame (never one of a record of crop_params)
+// is padding too, so no record makes a kernel read outside its maps.
+__device__ __forceinline__ bool crop_src(const CropParams &c, int o, int S, int H, int W, int &sy, int &sx) {
+  const int oy = o / S, ox = o - oy * S;
+  const int py = nearest_src(oy, c.S2, c.inv2), px = nearest_src(ox, c.S2, c.inv2);
+  const int iy = py - c.top, ix = px - c.left;
+  if (iy < 0 || iy >= c.h1 || ix < 0 || ix >= c.w1) return false;
+  sy = c.y1 + nearest_src(iy, c.h, c.inv1);
+  sx = c.x1 + nearest_src(ix, c.w, c.inv1);
+  return sy >= 0 && sy < H && sx >= 0 && sx < W;
+}
+
+// pixel o of the three S x S colour planes of one crop
+__device__ __forceinline__ void store_rgb_planes(float *crop, int o, int S, float r, float g, float b) {
+  const size_t plane = (size_t)S * S;
+  crop[o] = r;
+  crop[plane + o] = g;
+  crop[2 * plane + o] = b;
 }
 
 // The reference's square crop box, get_bbox (Pose_Estimation_Model/utils/data_utils.py:126-160), from the extent of a pixel set:

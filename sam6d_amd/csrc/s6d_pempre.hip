@@ -22,6 +22,11 @@
 //                    trip each).  Here one workgroup per detection walks its crop in chunks of 1024 pixels and compacts in
 //                    order (wave ballot ranks + a 16-entry wave prefix), writing to the detection's fixed-capacity slot.
 //   radius_filter    ``flag = norm(cloud - center) < radius * 1.2`` (:214-221) and the second in-order compaction, in place.
+//   crops            the masked colour crop of every surviving detection (:229-236): pem_crops_kernel<FrameCrops> of s6d_cv_resize.h.
+// The template twin is s6d_onboard.hip.  The two share, each written once: the count / extent reduction and the crop walk with its
+// compaction (s6d_compact.h), get_bbox (s6d_crop_params.h), the colour crop kernel (s6d_cv_resize.h).  Guards of both: a box that
+// does not lie inside the frame, or holds more than cap pixels, compacts to n = 0 with nothing written; its colour crop is that of a
+// black crop, (0 - mean) / std.  kept[k] is not checked.
 #include "s6d_common.h"
 #include "s6d_compact.h"
 #include "s6d_crop_params.h"
@@ -38,53 +43,25 @@ __global__ __launch_bounds__(kCmpThreads) void mask_boxes_kernel(const unsigned 
                                                                 const float *__restrict__ depth, int H, int W, long min_points,
                                                                 unsigned char *__restrict__ m, long *__restrict__ cnt_out,
                                                                 unsigned char *__restrict__ ok_out, long *__restrict__ box) {
-  __shared__ int s_cnt[kCmpThreads / 64], s_y0[kCmpThreads / 64], s_y1[kCmpThreads / 64], s_x0[kCmpThreads / 64],
-      s_x1[kCmpThreads / 64];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int p = blockIdx.x, tid = threadIdx.x;
   const size_t off = (size_t)p * H * W;
-  int cnt = 0, y0 = H, y1 = -1, x0 = W, x1 = -1;
+  int cnt = 0, b[4];
+  extent_init(b, H, W);
   for (int i = tid; i < H * W; i += kCmpThreads) {
     const bool v = mask[off + i] != 0 && depth[i] > 0.f;
     m[off + i] = v ? 1 : 0;
     if (v) {
-      const int y = i / W, x = i - y * W;
+      const int y = i / W;
       ++cnt;
-      y0 = min(y0, y);
-      y1 = max(y1, y);
-      x0 = min(x0, x);
-      x1 = max(x1, x);
+      extent_add(b, y, i - y * W);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o);
-    y0 = min(y0, __shfl_xor(y0, o));
-    y1 = max(y1, __shfl_xor(y1, o));
-    x0 = min(x0, __shfl_xor(x0, o));
-    x1 = max(x1, __shfl_xor(x1, o));
-  }
-  if (lane == 0) {
-    s_cnt[wave] = cnt;
-    s_y0[wave] = y0;
-    s_y1[wave] = y1;
-    s_x0[wave] = x0;
-    s_x1[wave] = x1;
-  }
-  __syncthreads();
+  const long c = block_extents<1>(cnt, b);
   if (tid == 0) {
-    long c = 0;
-    int ry0 = H, ry1 = -1, rx0 = W, rx1 = -1;
-    for (int w = 0; w < kCmpThreads / 64; ++w) {
-      c += s_cnt[w];
-      ry0 = min(ry0, s_y0[w]);
-      ry1 = max(ry1, s_y1[w]);
-      rx0 = min(rx0, s_x0[w]);
-      rx1 = max(rx1, s_x1[w]);
-    }
     const bool ok = c > min_points;
     cnt_out[p] = c;
     ok_out[p] = ok ? 1 : 0;
-    square_box(ok ? ry0 : 0, ok ? ry1 + 1 : H, ok ? rx0 : 0, ok ? rx1 + 1 : W, H, W, box + p * 4);
+    extent_box(ok, b, H, W, box + p * 4);
   }
 }
 
@@ -96,38 +73,18 @@ __global__ __launch_bounds__(kCmpThreads) void compact_cloud_kernel(const unsign
                                                                    float fx, float fy, float cx, float cy, long cap,
                                                                    int *__restrict__ choose, float *__restrict__ cloud,
                                                                    long *__restrict__ n_out) {
-  __shared__ unsigned wave_tot[kCmpThreads / 64];
-  __shared__ long base;
-  const int p = blockIdx.x, tid = threadIdx.x;
-  if (tid == 0) base = 0;
-  __syncthreads();
-  if (ok[p]) {
-    const long y1 = box[p * 4 + 0], y2 = box[p * 4 + 1], x1 = box[p * 4 + 2], x2 = box[p * 4 + 3];
-    const int bw = (int)(x2 - x1), area = (int)(y2 - y1) * bw;    // a crop is at most min(H,W)^2 pixels: 32-bit index arithmetic
-    const unsigned char *mp = m + (size_t)p * H * W;
-    for (int c0 = 0; c0 < area; c0 += kCmpThreads) {
-      const int j = c0 + tid;
-      bool keep = false;
-      int y = 0, x = 0;
-      if (j < area) {
-        const int r = j / bw;
-        y = (int)y1 + r;
-        x = (int)x1 + (j - r * bw);
-        keep = mp[y * W + x] != 0;
-      }
-      const long pos = block_rank(keep, &base, wave_tot);
-      if (keep) {
+  const int p = blockIdx.x;
+  const unsigned char *mp = m + (size_t)p * H * W;
+  compact_crop(
+      box + p * 4, ok[p] != 0, H, W, cap, n_out + p, [&](int pix) { return mp[pix] != 0; },
+      [&](long pos, int j, int y, int x) {
         const float z = depth[y * W + x];
         choose[(size_t)p * cap + pos] = j;
         float *c = cloud + ((size_t)p * cap + pos) * 3;
         c[0] = ((float)x - cx) * z / fx;
         c[1] = ((float)y - cy) * z / fy;
         c[2] = z;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid == 0) n_out[p] = base;
+      });
 }
 
 // in place: keep the points within lim[p] of center[p], in order.  choose (P,cap) i32, cloud (P,cap,3) f32, n (P) i64 in/out
@@ -249,33 +206,6 @@ __global__ __launch_bounds__(kSelThreads) void sample_indices_kernel(const float
   if (tid == 0) overflow[p] = 0;
 }
 
-// Masked colour crop of every surviving detection, resized to S x S and normalised (run_inference_custom.py:229-236:
-// uint8 crop * uint8 mask, cv2.resize(INTER_LINEAR), ToTensor + Normalize).  The resize is OpenCV's fixed-point algorithm for
-// CV_8U restated exactly (s6d_cv_resize.h, shared with the template crops of s6d_onboard.hip).
-// image (H,W,3) u8 RGB, m (P,H,W) u8, kept (M) i64, box (P,4) i64 -> out (M,3,S,S) f32, channel c = image channel 2 - c.
-__global__ void pem_crops_kernel(const unsigned char *__restrict__ image, const unsigned char *__restrict__ m,
-                                 const long *__restrict__ kept, const long *__restrict__ box, int M, int H, int W, int S,
-                                 int use_mask, float mean0, float mean1, float mean2, float std0, float std1, float std2,
-                                 float *__restrict__ out) {
-  const size_t total = (size_t)M * 3 * S * S;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int ox = (int)(i % S), oy = (int)((i / S) % S), c = (int)((i / ((size_t)S * S)) % 3), k = (int)(i / ((size_t)3 * S * S));
-    const long p = kept[k];
-    const long y1 = box[p * 4 + 0], y2 = box[p * 4 + 1], x1 = box[p * 4 + 2], x2 = box[p * 4 + 3];
-    const long h = y2 - y1, w = x2 - x1;
-    const int ch = 2 - c;
-    const unsigned char *mp = m + (size_t)p * H * W;
-    auto px = [&](long yy, long xx) -> int {                           // uint8 crop * uint8 mask of the reference
-      const long y = y1 + yy, x = x1 + xx;
-      const int v = (int)image[(y * W + x) * 3 + ch];
-      return use_mask ? (mp[y * W + x] ? v : 0) : v;
-    };
-    const int g = cv_resize_linear_px(px, oy, ox, h, w, S);
-    const float mean = c == 0 ? mean0 : (c == 1 ? mean1 : mean2), sd = c == 0 ? std0 : (c == 1 ? std1 : std2);
-    out[i] = ((float)g / 255.f - mean) / sd;
-  }
-}
-
 }  // namespace s6d
 
 using namespace s6d;
@@ -297,7 +227,7 @@ extern "C" int s6d_pem_sample_indices_f32(const float *keys, long key_stride, co
 extern "C" int s6d_pem_compact_cloud_f32(const unsigned char *m, const float *depth, const int64_t *box, const unsigned char *ok,
                                          int P, int H, int W, float fx, float fy, float cx, float cy, long cap, int32_t *choose,
                                          float *cloud, int64_t *n, void *stream) {
-  if (P < 0 || H <= 0 || W <= 0 || cap <= 0 || fx == 0.f || fy == 0.f) return S6D_EINVAL;
+  if (P < 0 || H <= 0 || W <= 0 || (long)H * W > 0x7fffffffL || cap <= 0 || fx == 0.f || fy == 0.f) return S6D_EINVAL;
   if (P == 0) return S6D_OK;
   if (!m || !depth || !box || !ok || !choose || !cloud || !n) return S6D_EINVAL;
   hipLaunchKernelGGL(compact_cloud_kernel, dim3((unsigned)P), dim3(kCmpThreads), 0, as_stream(stream), m, depth,
@@ -328,14 +258,14 @@ extern "C" int s6d_pem_mask_boxes_u8(const unsigned char *mask, const float *dep
 extern "C" int s6d_pem_crops_f32(const unsigned char *image, const unsigned char *m, const int64_t *kept, const int64_t *box,
                                  int M, int H, int W, int S, int use_mask, const float *mean3_host, const float *std3_host,
                                  float *out, void *stream) {
-  if (M < 0 || H <= 0 || W <= 0 || S <= 0) return S6D_EINVAL;
+  if (M < 0 || H <= 0 || W <= 0 || S <= 0 || (long)H * W > 0x7fffffffL) return S6D_EINVAL;
   if (M == 0) return S6D_OK;
   if (!image || !m || !kept || !box || !mean3_host || !std3_host || !out) return S6D_EINVAL;
   const size_t total = (size_t)M * 3 * S * S;
   size_t g = (total + 255) / 256;
   if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(pem_crops_kernel, dim3((unsigned)g), dim3(256), 0, as_stream(stream), image, m, (const long *)kept,
-                     (const long *)box, M, H, W, S, use_mask, mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0],
-                     std3_host[1], std3_host[2], out);
+  const FrameCrops src{image, m, (const long *)kept};
+  hipLaunchKernelGGL(pem_crops_kernel<FrameCrops>, dim3((unsigned)g), dim3(256), 0, as_stream(stream), src, (const long *)box, M, H,
+                     W, S, use_mask, mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0], std3_host[1], std3_host[2], out);
   return launch_status();
 }

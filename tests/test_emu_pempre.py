@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from sam6d_amd.pem import preprocess as pre
+from tests import test_gpu_pem_pre as T
 
 
 def _lib_path(n, keys, n_sample, monkeypatch):
@@ -59,10 +60,7 @@ def test_full_frame_with_the_kernel_sampler_matches_the_oracle(emu, monkeypatch)
     np.testing.assert_array_equal(out["rgb_choose"].numpy(), ref["rgb_choose"])
 
 
-def _frame(P=8, seed=3):
-    from sam6d_amd.utils import synth
-    inp = synth.pem_pre_inputs(P=P, seed=seed)
-    return inp, (torch.from_numpy(inp["image"]), inp["depth"], inp["K"], inp["masks"])
+_frame = T._frame
 
 
 def test_kernel_path_of_the_whole_preprocessing_matches_the_oracle(emu, monkeypatch):
@@ -105,64 +103,30 @@ def test_kernel_path_with_no_survivor_and_with_empty_masks(emu, monkeypatch):
     assert 1 not in out["kept"].tolist() and out["pts"].shape[1:] == (256, 3)
 
 
+# ---- the kernels called directly: the bodies are those of tests/test_gpu_pem_pre.py, here on the emulator ----------------------------
 def test_mask_boxes_kernel_equals_the_library_ops(emu):
-    """s6d_pem_mask_boxes_u8 against mask AND depth / count / square_boxes of the library path (itself pinned to the
-    reference's get_bbox), incl. empty masks, masks touching the frame edge and a detection below the point threshold."""
-    g = torch.Generator().manual_seed(4)
-    P, H, W = 9, 48, 64
-    masks = torch.zeros(P, H, W, dtype=torch.bool)
-    for i, (y1, y2, x1, x2) in enumerate([(0, 48, 0, 64), (0, 5, 0, 64), (10, 40, 60, 64), (47, 48, 0, 1), (5, 45, 3, 9), (20, 21, 10, 50),
-                                          (0, 0, 0, 0), (3, 44, 2, 63), (12, 30, 12, 30)]):
-        masks[i, y1:y2, x1:x2] = torch.rand(y2 - y1, x2 - x1, generator=g) > 0.3
-    depth = torch.rand(H, W, generator=g)
-    depth[depth < 0.2] = 0.0
-    m8, cnt, ok8, box = emu.pem_mask_boxes(masks.view(torch.uint8), depth, 32)
-    m = masks & (depth > 0)[None]
-    ok = m.flatten(1).sum(1) > 32
-    assert torch.equal(m8.bool(), m) and torch.equal(cnt, m.flatten(1).sum(1)) and torch.equal(ok8.bool(), ok)
-    assert 0 < int(ok.sum()) < P                                     # both kinds present
-    assert torch.equal(box, pre.square_boxes(m | ~ok[:, None, None]))
+    T.mask_boxes_body(emu, "cpu")
 
 
 def test_crops_kernel_equals_the_library_statement(emu):
-    """s6d_pem_crops_f32 against preprocess._crops, value for value (same float32 operations in the same order)."""
-    inp, (image, depth, K, masks) = _frame()
-    m = masks & (depth > 0)[None]
-    box = pre.square_boxes(m)
-    kept = torch.tensor([6, 0, 2, 5])
-    for flag in (True, False):
-        want = pre._crops(image, m[kept].float(), box[kept], 224, flag)
-        got = emu.pem_crops(image.contiguous(), m.to(torch.uint8), kept, box, 224, flag, pre.MEAN, pre.STD)
-        assert torch.equal(got, want), (got - want).abs().max()
-    want = pre._crops(image, m[kept].float(), box[kept], 56, True)
-    assert torch.equal(emu.pem_crops(image.contiguous(), m.to(torch.uint8), kept, box, 56, True, pre.MEAN, pre.STD), want)
+    T.crops_library_body(emu, "cpu")
 
 
 def test_crops_follow_the_cv2_restatement_at_every_ratio(emu):
-    """s6d_pem_crops_f32 and preprocess._crops against oracle.pem_pre.cv2_resize_linear_u8 (cv2.resize INTER_LINEAR restated),
-    value for value, at the ratios with their own code path: 1:1 (copy), exactly 2:1 (box mean), up- and down-scaling with odd
-    sides, a crop touching the frame border."""
-    import numpy as np
+    T.crops_cv2_body(emu, "cpu")
 
-    from oracle import pem_pre as o
-    from sam6d_amd.pem import preprocess as pre
-    S = 16
-    H, W = 72, 80
-    g = torch.Generator().manual_seed(11)
-    image = torch.randint(0, 256, (H, W, 3), generator=g, dtype=torch.uint8)
-    sides = [16, 32, 7, 23, 48, 33, 5]
-    box = torch.tensor([[y, y + n, x, x + n] for n, (y, x) in zip(sides, [(0, 0), (10, 20), (3, 70), (40, 5), (24, 32), (39, 47), (67, 75)])])
-    m = torch.zeros(len(sides), H, W, dtype=torch.uint8)
-    for i, (y1, y2, x1, x2) in enumerate(box.tolist()):
-        m[i, y1:y2, x1:x2] = (torch.rand(y2 - y1, x2 - x1, generator=g) > 0.3).to(torch.uint8)
-    kept = torch.arange(len(sides))
-    for flag in (True, False):
-        got = emu.pem_crops(image.contiguous(), m, kept, box, S, flag, pre.MEAN, pre.STD)
-        lib = pre._crops(image, m, box, S, flag)
-        assert torch.equal(got, lib)
-        for i, (y1, y2, x1, x2) in enumerate(box.tolist()):
-            rgb = image.numpy()[y1:y2, x1:x2, :][:, :, ::-1]
-            if flag:
-                rgb = rgb * (m[i].numpy()[y1:y2, x1:x2, None] > 0).astype(np.uint8)
-            want = (o.cv2_resize_linear_u8(rgb, S).astype(np.float32) / np.float32(255) - o.MEAN) / o.STD
-            assert np.array_equal(got[i].numpy(), want.transpose(2, 0, 1)), (i, flag)
+
+def test_compact_cloud_kernel_in_crop_order_with_the_reference_back_projection(emu):
+    T.compact_cloud_body(emu, "cpu")
+
+
+def test_compaction_skips_a_box_outside_the_frame_or_larger_than_a_slot(emu):
+    T.compact_guards_body(emu, "cpu")
+
+
+def test_crop_of_a_box_outside_the_frame_is_a_black_crop(emu):
+    T.crops_guard_body(emu, "cpu")
+
+
+def test_crop_resize_pad_source_outside_the_frame_is_padding(emu):
+    T.crop_resize_pad_guard_body(emu, "cpu")
