@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 135
+#define S6D_ABI_VERSION 136
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -266,6 +266,26 @@ int s6d_pose_err_mssd_mspd_f32(const float *vertices, const float *est, const fl
 int s6d_vsd_counts_f32(const float *depth_est, const float *depth_gt, const float *depth_test, const int32_t *test_index,
                        const float *cams, const float *scale, int N, int M, int H, int W, float delta, const float *taus_host,
                        int NT, int32_t *uni, int32_t *inter, int32_t *ge, void *stream);
+
+/* BOP ground truth from annotated poses (csrc/s6d_bopgt.hip): masks, visible masks, pixel counts and extents of N instances.
+ * canvas (N, H + 2 my, W + 2 mx) f32: camera Z of each instance, 0 on background = s6d_raster_depth_f32 at that size with cx + mx,
+ * cy + my; image pixel (u, v) is canvas pixel (u + mx, v + my).  depth_test (M,H,W) f32 measured depth in model units (0 = missing),
+ * test_index (N) into M, cams (N,4) = fx fy cx cy of the IMAGE.  In float32, every operation rounded once:  all = Zg > 0 on the
+ * canvas;  inside the window  mask = all,  r = sqrtf((a a + b b) + 1) with a = ((float)u - cx) / fx, b = ((float)v - cy) / fy,
+ * Dg = Zg r, Dt = Zt r,  valid = mask && Zt > 0,  visib = mask && ((Dg - Dt) <= delta || Zt == 0)  (vis_gt of s6d_vsd_counts_f32,
+ * one device function).  mask, mask_visib (N,H,W) uint8 0 / 1;  counts (N,4) i32 = all, in-image, valid, visib;  extents (N,2,4) i32 =
+ * xmin ymin xmax ymax, maximum inclusive, in image coordinates (may be negative or >= W), row 0 of `all`, row 1 of `visib`, an empty
+ * set INT_MAX INT_MAX INT_MIN INT_MIN.  Integer atomics: the same result alone, in a batch and under any chunking.  A test_index
+ * outside [0, M) leaves the instance's counts 0, extents empty and masks 0.  mx, my >= 0; (H + 2 my)(W + 2 mx) < 2^31,
+ * S6D_EUNSUPPORTED otherwise. */
+int s6d_gt_visibility_f32(const float *canvas, const float *depth_test, const int32_t *test_index, const float *cams, int N, int M,
+                          int H, int W, int mx, int my, float delta, uint8_t *mask, uint8_t *mask_visib, int32_t *counts,
+                          int32_t *extents, void *stream);
+
+/* Diameter of a model: vertices (V,3) f32 -> diameter[0] = sqrtf of the maximum over all vertex pairs of (dx dx + dy dy) + dz dz
+ * (float32, contraction off; one sqrtf, of the maximum).  A squared distance that is not finite counts as +inf.  V = 1 gives 0;
+ * V < 1 is S6D_EINVAL.  Tiles of 256 vertices, persistent workgroups over the tile pairs; no (V,V) buffer and no workspace. */
+int s6d_model_diameter_f32(const float *vertices, int V, float *diameter, void *stream);
 
 /* ---------------------------------------------------------------- COCO AP of ISM results (csrc/s6d_cocoeval.hip)
  * The device stages of the detection / segmentation AP as DEFINED in sam6d_amd/evaluation.py: integers for the

@@ -32,7 +32,7 @@
 //              zeroed outputs.  Integer sums do not depend on their order: the counts are exact and reproducible.
 //              The caller forms e_k = (ge_k + union - inter) / union in float64 (1 when union = 0).
 //              A test_index outside [0, M) leaves the pair's counts at zero (the wrapper refuses it on the host).
-#include "s6d_common.h"
+#include "s6d_bopvis.h"
 
 namespace s6d {
 
@@ -133,10 +133,9 @@ __global__ __launch_bounds__(BE_THREADS) void vsd_counts_kernel(const float *__r
   for (long p = p0 + threadIdx.x; p < p1; p += BE_THREADS) {
     const int v = (int)(p / W), u = (int)(p - (long)v * W);
     const float ze = ZE[p], zg = ZG[p], zt = ZT[p];
-    const float a = ((float)u - cx) / fx, b = ((float)v - cy) / fy;
-    const float r = sqrtf((a * a + b * b) + 1.0f);
+    const float r = bop_ray_factor(u, v, fx, fy, cx, cy);
     const float De = ze * r, Dg = zg * r, Dt = zt * r;
-    const bool vis_gt = zg > 0.f && ((Dg - Dt) <= delta || zt == 0.f);
+    const bool vis_gt = bop_visible(zg, zt, Dg, Dt, delta);          // csrc/s6d_bopvis.h: the statement gt_visibility_kernel shares
     const bool vis_est = ze > 0.f && (((De - Dt) <= delta || zt == 0.f) || vis_gt);
     cnt[0] += (vis_gt || vis_est) ? 1 : 0;
     if (vis_gt && vis_est) {

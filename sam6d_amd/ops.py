@@ -875,6 +875,51 @@ def vsd_counts(depth_est, depth_gt, depth_test, test_index, cams, delta, taus, s
     return union, inter, ge
 
 
+# ------------------------------------------------------------------ BOP ground truth from poses (csrc/s6d_bopgt.hip)
+def gt_visibility(canvas, depth_test, test_index, cams, delta, margin=(0, 0)):
+    """canvas (N, H + 2 my, W + 2 mx) f32 = ``render_depth`` of every instance at that size with cx + mx, cy + my (camera Z, 0 on
+    background), depth_test (M,H,W) f32 measured depth in the same unit (0 = missing), test_index (N,) int32 into M, cams (N,4) f32
+    = fx fy cx cy of the IMAGE, delta, margin = (mx, my) >= 0 ->
+    dict(mask, mask_visib (N,H,W) uint8 0 / 1; counts (N,4) int32 = all (canvas), in-image, valid, visib; extents (N,2,4) int32 =
+    xmin ymin xmax ymax inclusive in image coordinates, row 0 of the object on the canvas, row 1 of the visible part, an empty set
+    INT_MAX INT_MAX INT_MIN INT_MIN) (include/sam6d_hip.h: s6d_gt_visibility_f32).  A test_index outside [0, M) is refused here, on
+    the host."""
+    _chk(canvas, torch.float32, "canvas", 3)
+    _chk(depth_test, torch.float32, "depth_test", 3)
+    _chk(test_index, torch.int32, "test_index", 1)
+    _chk(cams, torch.float32, "cams", 2)
+    mx, my = (int(m) for m in margin)
+    if mx < 0 or my < 0:
+        raise ValueError(f"gt_visibility: margin must be >= 0, got {(mx, my)}")
+    N, M, H, W = canvas.shape[0], depth_test.shape[0], depth_test.shape[1], depth_test.shape[2]
+    if tuple(canvas.shape[1:]) != (H + 2 * my, W + 2 * mx) or M < 1 or H < 1 or W < 1 or tuple(test_index.shape) != (N,) or \
+            tuple(cams.shape) != (N, 4):
+        raise ValueError(f"gt_visibility: canvas (N,H+2my,W+2mx), depth_test (M,H,W), test_index (N,), cams (N,4) expected, got "
+                         f"{tuple(canvas.shape)}, {tuple(depth_test.shape)}, {tuple(test_index.shape)}, {tuple(cams.shape)} with margin {(mx, my)}")
+    if (H + 2 * my) * (W + 2 * mx) >= 2 ** 31:
+        raise ValueError(f"gt_visibility: a canvas of {(H + 2 * my) * (W + 2 * mx)} pixels (2^31 or more) is refused")
+    if N and (int(test_index.min()) < 0 or int(test_index.max()) >= M):
+        raise ValueError(f"gt_visibility: test_index must lie in [0, {M}), got [{int(test_index.min())}, {int(test_index.max())}]")
+    dev = canvas.device
+    out = dict(mask=torch.empty(N, H, W, dtype=torch.uint8, device=dev), mask_visib=torch.empty(N, H, W, dtype=torch.uint8, device=dev),
+               counts=torch.empty(N, 4, dtype=torch.int32, device=dev), extents=torch.empty(N, 2, 4, dtype=torch.int32, device=dev))
+    _call("s6d_gt_visibility_f32", _ptr(canvas), _ptr(depth_test), _ptr(test_index), _ptr(cams), N, M, H, W, mx, my, float(delta),
+          _ptr(out["mask"]), _ptr(out["mask_visib"]), _ptr(out["counts"]), _ptr(out["extents"]), _stream())
+    return out
+
+
+def model_diameter(vertices):
+    """vertices (V,3) f32, V >= 1 -> (1,) f32: the largest distance between two vertices, sqrtf of the maximum of
+    (dx dx + dy dy) + dz dz over all pairs; +inf when a squared distance is not finite (include/sam6d_hip.h:
+    s6d_model_diameter_f32).  No (V,V) buffer is made."""
+    _chk(vertices, torch.float32, "vertices", 2)
+    if vertices.shape[1] != 3 or vertices.shape[0] < 1:
+        raise ValueError(f"model_diameter: vertices (V,3) with V >= 1 expected, got {tuple(vertices.shape)}")
+    out = torch.empty(1, dtype=torch.float32, device=vertices.device)
+    _call("s6d_model_diameter_f32", _ptr(vertices), vertices.shape[0], _ptr(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------ pose refinement against the depth (csrc/s6d_refine.hip)
 RF_CHUNK = _lib.header_constant("S6D_RF_CHUNK")          # pixels one workgroup of the normal-equation kernel sums (its reduction order)
 RF_TERMS = 28                                            # 21 upper entries of J J^T, 6 of J r, r r
@@ -1918,6 +1963,7 @@ def have(name):
                "template_boxes": "s6d_template_boxes_u8", "template_points": "s6d_template_points_f32", "template_pem_crops": "s6d_template_pem_crops_f32",
                "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32", "render_views_textured": "s6d_raster_views_tex_f32",
                "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32",
+               "gt_visibility": "s6d_gt_visibility_f32", "model_diameter": "s6d_model_diameter_f32",
                "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match",
                "small_regions": "s6d_remove_small_regions_u8",
                "rle_encode": "s6d_rle_write_u8", "rle_to_packed": "s6d_rle_to_packed", "rle_to_masks": "s6d_rle_to_masks_u8",

@@ -1,6 +1,6 @@
 """Score a BOP result file with sam6d_amd.evaluation (MSSD, MSPD, VSD and their average recall, BOP19 parameters):
 
-python tools/bop_eval.py --results X.csv --dataset DIR [--split test] [--device cuda|cpu]
+python tools/bop_eval.py --results X.csv --dataset DIR [--split test] [--device cuda|cpu] [--derive-gt]
 
 X.csv: the lines ``pem.results.write_bop_csv`` writes (``scene,im,obj,score,R,t,time``; what FramePipeline and tools/run_sharded.py
 produce).  DIR: a dataset in the BOP layout --
@@ -9,6 +9,9 @@ produce).  DIR: a dataset in the BOP layout --
                                                                                     DIR/<split>)
   DIR/<split>/<scene:06d>/scene_gt_info.json   optional: the targets are the ground truths with visib_fract >= 0.1; all of them when
                                                the file is absent
+--derive-gt: where models_eval/models_info.json or a scene's scene_gt_info.json is absent, the diameter and the visib_fract of the
+ground truths are derived in memory from the meshes, the poses and the depth images (sam6d_amd.groundtruth; what tools/bop_gt.py
+writes); without the flag the tool behaves as described above.
 Every image named in the scenes' ground truth that the result file's scenes cover is scored; depth PNGs are 16 bit, times
 ``depth_scale`` = millimetres.  Prints one JSON line.
 
@@ -44,15 +47,19 @@ def walk_scenes(root, split, scenes):
             yield scene, im, d, scene_gt[im], None if gt_info is None else gt_info[im], scene_cam[im]
 
 
-def load_dataset(root, split, scenes, min_visib=0.1):
-    """-> (models {obj: dict}, ground_truths dict, images dict, index {(scene, im): image number})."""
+def load_dataset(root, split, scenes, min_visib=0.1, derive_gt=False, device=None):
+    """-> (models {obj: dict}, ground_truths dict, images dict, index {(scene, im): image number}).  ``derive_gt``: a missing
+    models_info.json and the visib_fract of scenes without scene_gt_info.json come from ``sam6d_amd.groundtruth`` (on ``device``)."""
     from PIL import Image
 
     from sam6d_amd import render
-    with open(os.path.join(root, "models_eval", "models_info.json")) as f:
-        info = {int(k): v for k, v in json.load(f).items()}
+    info = None
+    if not derive_gt or os.path.exists(os.path.join(root, "models_eval", "models_info.json")):
+        with open(os.path.join(root, "models_eval", "models_info.json")) as f:
+            info = {int(k): v for k, v in json.load(f).items()}
     index, cams, depths = {}, [], []
     gt = dict(im=[], obj=[], pose=[])
+    derived = []                                                           # positions in gt whose visib_fract is still to be derived
     for scene, im, d, records, gt_info, cam in walk_scenes(root, split, scenes):
         K = np.asarray(cam["cam_K"], np.float64).reshape(3, 3)
         depth = np.asarray(Image.open(os.path.join(d, "depth", f"{im:06d}.png")), np.float32) * np.float32(cam.get("depth_scale", 1.0))
@@ -65,6 +72,8 @@ def load_dataset(root, split, scenes, min_visib=0.1):
             P = np.eye(4)
             P[:3, :3] = np.asarray(g["cam_R_m2c"], np.float64).reshape(3, 3)
             P[:3, 3] = np.asarray(g["cam_t_m2c"], np.float64).reshape(3)
+            if gt_info is None and derive_gt:
+                derived.append(len(gt["im"]))
             gt["im"].append(index[(scene, im)])
             gt["obj"].append(int(g["obj_id"]))
             gt["pose"].append(P)
@@ -73,9 +82,21 @@ def load_dataset(root, split, scenes, min_visib=0.1):
     models = {}
     for obj in sorted(set(gt["obj"])):
         v, f, _ = render.load_ply(os.path.join(root, "models_eval", f"obj_{obj:06d}.ply"))
-        models[obj] = dict(vertices=v, faces=f, info=info[obj], diameter=float(info[obj]["diameter"]))
+        if info is None:
+            from sam6d_amd import groundtruth
+            rec = groundtruth.model_info(v, device=device)
+        else:
+            rec = info[obj]
+        models[obj] = dict(vertices=v, faces=f, info=rec, diameter=float(rec["diameter"]))
     images = dict(cams=np.asarray(cams, np.float32).reshape(-1, 4), depth=np.stack(depths) if depths else np.zeros((0, 1, 1), np.float32))
     gt = dict(im=np.asarray(gt["im"], np.int64), obj=np.asarray(gt["obj"], np.int64), pose=np.asarray(gt["pose"], np.float64).reshape(-1, 4, 4))
+    if derived:
+        from sam6d_amd import groundtruth
+        sel = np.asarray(derived, np.int64)
+        res = groundtruth.instance_ground_truth(models, {k: v[sel] for k, v in gt.items()}, images, device=device)
+        keep = np.ones(len(gt["im"]), bool)
+        keep[sel] = res["visib_fract"] >= min_visib
+        gt = {k: v[keep] for k, v in gt.items()}
     return models, gt, images, index
 
 
@@ -85,11 +106,12 @@ def main(argv=None):
     ap.add_argument("--dataset", required=True)
     ap.add_argument("--split", default="test")
     ap.add_argument("--device", default=None, help="cuda (kernels) or cpu (the torch statements); default: cuda when there is one")
+    ap.add_argument("--derive-gt", action="store_true", help="derive a missing models_info.json / scene_gt_info.json in memory")
     a = ap.parse_args(argv)
     from sam6d_amd import evaluation
     t0 = time.time()
     res = evaluation.read_bop_csv(a.results)
-    models, gt, images, index = load_dataset(a.dataset, a.split, set(res["scene"].tolist()))
+    models, gt, images, index = load_dataset(a.dataset, a.split, set(res["scene"].tolist()), derive_gt=a.derive_gt, device=a.device)
     keep = np.array([(int(s), int(i)) in index for s, i in zip(res["scene"], res["im"])], bool)
     pose = np.tile(np.eye(4), (int(keep.sum()), 1, 1))
     pose[:, :3, :3], pose[:, :3, 3] = res["R"][keep], res["t"][keep]
