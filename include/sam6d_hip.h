@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 136
+#define S6D_ABI_VERSION 137
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -286,6 +286,31 @@ int s6d_gt_visibility_f32(const float *canvas, const float *depth_test, const in
  * (float32, contraction off; one sqrtf, of the maximum).  A squared distance that is not finite counts as +inf.  V = 1 gives 0;
  * V < 1 is S6D_EINVAL.  Tiles of 256 vertices, persistent workgroups over the tile pairs; no (V,V) buffer and no workspace. */
 int s6d_model_diameter_f32(const float *vertices, int V, float *diameter, void *stream);
+
+/* ---------------------------------------------------------------- ADD / ADD-S pose errors (csrc/s6d_adderr.hip)
+ * N (estimate, ground truth) pose pairs of ONE object, as DEFINED in csrc/s6d_adderr.hip, operation by operation in float32 with one
+ * rounding each; no equality with bop_toolkit or any other tool is claimed.  vertices (V,3) f32 model units, est, gts (N,4,4) f32
+ * object -> camera ->
+ *   per_vertex (N,V) f32, optional (NULL: the values go to `workspace`):
+ *     ADD    a_i = sqrtf((dx dx + dy dy) + dz dz),  d = E v_i - G v_i
+ *     ADD-S  s_i = sqrtf(min_j d2(E v_i, G v_j)),  the minimum on the bits of the non-negative floats, no (V,V) buffer
+ *     with X = ((r00 vx + r01 vy) + r02 vz) + tx; a squared distance that is not finite (NaN included) counts as +inf
+ *   mean (N) f64 = (sum_i (double)value_i) / (double)V in the fixed order of csrc/s6d_adderr.hip (256 lanes striding, xor butterfly,
+ *     waves in order); +inf when a value is +inf, never NaN
+ *   max (N) f32 = max_i value_i (for ADD-S the one-sided Hausdorff distance).
+ * The per-vertex values are always materialised and the reduction reads them: an estimate has the same bits alone, in a batch,
+ * under any chunking over N and under any setting of s6d_set_adds_sources_per_lane.  workspace: needed when per_vertex is NULL,
+ * s6d_pose_err_adds_workspace_bytes(N, V) bytes (both entry points), 4-byte aligned.  V >= 1, N >= 0 (N == 0: S6D_OK, nothing is
+ * looked at); N * V < 2^31, S6D_EUNSUPPORTED otherwise. */
+int s6d_pose_err_add_f32(const float *vertices, int V, const float *est, const float *gts, int N, float *per_vertex, double *mean,
+                         float *max, void *workspace, void *stream);
+int s6d_pose_err_adds_f32(const float *vertices, int V, const float *est, const float *gts, int N, float *per_vertex, double *mean,
+                          float *max, void *workspace, void *stream);
+long s6d_pose_err_adds_workspace_bytes(int N, int V);   /* -1 for sizes the entry points refuse */
+/* Source vertices each lane of the ADD-S all-pairs kernel keeps in registers: 1, 2 or 4; 0 = the library's choice (the default,
+ * measured in profiles/add_eval.md).  Every setting gives the same bits; the switch exists for measurements and the tests.
+ * Process-wide; other values: S6D_EINVAL. */
+int s6d_set_adds_sources_per_lane(int sources);
 
 /* ---------------------------------------------------------------- COCO AP of ISM results (csrc/s6d_cocoeval.hip)
  * The device stages of the detection / segmentation AP as DEFINED in sam6d_amd/evaluation.py: integers for the

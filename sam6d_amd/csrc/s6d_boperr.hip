@@ -9,7 +9,8 @@
 // pose_err_kernel   one workgroup of 256 lanes per (estimate n, symmetry s); E = est[n], G = gts[n][s] (the ground truth already
 //                   composed with the symmetry, on the host in float64, rounded once); fx fy cx cy = cams[n].
 //   transform  for pose rows (r00 r01 r02 tx; ...) and a vertex v:  X = ((r00 vx + r01 vy) + r02 vz) + tx,  Y and Z alike
-//              (the rasteriser's vertex statement), once with E and once with G.
+//              (the rasteriser's vertex statement; pose_err_transform of csrc/s6d_bopvis.h, which ADD / ADD-S share), once with E
+//              and once with G.
 //   MSSD       d3 = (dx dx + dy dy) + dz dz  with  dx = Xe - Xg, ...;  a d3 that is not finite (NaN included) counts as +inf.
 //   MSPD       x = (fx X) / Z + cx,  y = (fy Y) / Z + cy  for both poses;  d2 = du du + dv dv  with  du = xe - xg, dv = ye - yg;
 //              a vertex with Z <= 0 (or NaN) in either pose, or a d2 that is not finite, counts as +inf.
@@ -52,13 +53,6 @@ struct VsdTaus {
 __global__ __launch_bounds__(BE_THREADS) void pose_err_fill_kernel(unsigned *__restrict__ a, unsigned *__restrict__ b, int n) {
   const int i = blockIdx.x * BE_THREADS + threadIdx.x;
   if (i < n) a[i] = b[i] = BE_INF_BITS;
-}
-
-__device__ __forceinline__ void pose_err_transform(const float *__restrict__ P, float vx, float vy, float vz, float &X, float &Y,
-                                                   float &Z) {
-  X = ((P[0] * vx + P[1] * vy) + P[2] * vz) + P[3];
-  Y = ((P[4] * vx + P[5] * vy) + P[6] * vz) + P[7];
-  Z = ((P[8] * vx + P[9] * vy) + P[10] * vz) + P[11];
 }
 
 __global__ __launch_bounds__(BE_THREADS) void pose_err_kernel(const float *__restrict__ vertices, const float *__restrict__ est,

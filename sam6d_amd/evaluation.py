@@ -18,6 +18,11 @@ vertices of its evaluation model):
         score (``match_and_recall``); the recall is averaged over the thresholds (and the taus), AR over the three errors
         (``bop19_scores``).
 
+  ADD   mean_i |E v_i - G v_i|;  ADD-S  mean_i min_j |E v_i - G v_j|  (``add_errors``; csrc/s6d_adderr.hip states the float32
+        operations, the minimum on the bits and the fixed-order float64 mean); per target the error of the estimate assigned to it
+        (``assign_errors``), recall below a fraction of the diameter and the AUC over absolute thresholds (``add_scores``: ADD,
+        ADD-S, and ADD(-S) = ADD-S for objects with a symmetry set); ``symmetry_residuals`` checks a symmetry set against its mesh.
+
 Every error function goes through ``policy.guard("eval.<name>", ...)``: kernels on device tensors, the torch statements below
 otherwise (policy field ``bop_eval`` = "0", or CPU tensors).  The torch branch is chunked over the symmetries, so it does not
 hold the (N, S, V, 3) tensor either.
@@ -175,6 +180,222 @@ def mspd(vertices, est, gt, syms, cams):
     """Maximum symmetry-aware projection distance of N estimates of one object -> (N,) float32, pixels; +inf where a vertex lies
     at Z <= 0 under every symmetry."""
     return pose_errors(vertices, est, gt, syms, cams, site="eval.mspd")[1]
+
+
+# ------------------------------------------------------------------------------------------------------------------- ADD / ADD-S
+ADD_LANES, ADD_WAVE = 256, 64          # the summation order of csrc/s6d_adderr.hip: 256 lanes striding, waves of 64
+
+
+def _row_mean_fixed(values):
+    """(N,V) float32 -> (N,) float64: the mean in the FIXED order of row_mean_max_kernel.  Lane l adds i = l, l + 256, ... from +0
+    (a row is padded with +0, which changes no sum), the wave by the xor butterfly x += x[lane ^ o], o = 32 .. 1, the waves in
+    order ((w0 + w1) + w2) + w3; one division by V."""
+    N, V = values.shape
+    K = -(-V // ADD_LANES)
+    x = torch.zeros(N, K * ADD_LANES, dtype=torch.float64, device=values.device)
+    x[:, :V] = values.double()
+    x = x.view(N, K, ADD_LANES)
+    acc = torch.zeros(N, ADD_LANES, dtype=torch.float64, device=values.device)
+    for k in range(K):
+        acc = acc + x[:, k]
+    acc = acc.view(N, ADD_LANES // ADD_WAVE, ADD_WAVE)
+    lane = torch.arange(ADD_WAVE, device=values.device)
+    o = ADD_WAVE // 2
+    while o:
+        acc = acc + acc[:, :, lane ^ o]
+        o //= 2
+    s = acc[:, 0, 0]
+    for w in range(1, ADD_LANES // ADD_WAVE):
+        s = s + acc[:, w, 0]
+    return s / torch.full_like(s, float(V))          # a tensor divisor: one IEEE division (a scalar one becomes a product by 1 / V on the device)
+
+
+def _add_errors_library(vertices, est, gts, which=("add", "adds"), chunk_bytes=1 << 26):
+    """The library statement of ``ops.add_errors`` (its dict, the per-vertex values always given): the same float32 operations, a
+    chunk of source rows against all target vertices at a time -- never an (N, V, V) tensor."""
+    V, N = vertices.shape[0], est.shape[0]
+    vx, vy, vz = vertices[:, 0], vertices[:, 1], vertices[:, 2]
+    inf = torch.tensor(float("inf"), device=est.device)
+
+    def transform(P):                                                      # three (N,V): X = ((r00 vx + r01 vy) + r02 vz) + tx
+        return [((P[:, r, 0, None] * vx + P[:, r, 1, None] * vy) + P[:, r, 2, None] * vz) + P[:, r, 3, None] for r in range(3)]
+
+    def root(d2):                                                          # the correctly rounded float32 root: through float64 (53 >= 2 * 24 + 2
+        return torch.sqrt(torch.where(torch.isfinite(d2), d2, inf).double()).float()   # bits), torch's vectorised float32 sqrt is not
+
+    E, G = transform(est), transform(gts)
+    out = dict(add=None, add_max=None, add_per_vertex=None, adds=None, adds_max=None, adds_per_vertex=None)
+    for name in which:
+        if name == "add":
+            dx, dy, dz = E[0] - G[0], E[1] - G[1], E[2] - G[2]
+            pv = root((dx * dx + dy * dy) + dz * dz)
+        elif name == "adds":
+            pv = torch.empty(N, V, dtype=torch.float32, device=est.device)
+            step = max(1, chunk_bytes // (16 * V))
+            for n in range(N):
+                for i in range(0, V, step):
+                    dx, dy, dz = (E[c][n, i:i + step, None] - G[c][n, None, :] for c in range(3))
+                    d2 = (dx * dx + dy * dy) + dz * dz
+                    pv[n, i:i + step] = root(torch.where(torch.isfinite(d2), d2, inf).min(1)[0])
+        else:
+            raise ValueError(f"add_errors: which names 'add' and 'adds', got {name!r}")
+        out[name + "_per_vertex"], out[name], out[name + "_max"] = pv, _row_mean_fixed(pv), pv.max(1)[0]
+    return out
+
+
+@torch.no_grad()
+def add_errors(vertices, est, gt, which=("add", "adds"), chunk_bytes=1 << 28, per_vertex=False):
+    """ADD and ADD-S of N (estimate, ground truth) pose pairs of ONE object, as defined in csrc/s6d_adderr.hip: vertices (V,3),
+    est, gt (N,4,4) object -> camera, translation in model units -> dict of tensors on the device of ``est``:
+    add, adds (N,) float64 = the mean over the vertices of |E v_i - G v_i| and of min_j |E v_i - G v_j|; add_max, adds_max (N,)
+    float32 (adds_max: the one-sided Hausdorff distance); add_per_vertex, adds_per_vertex (N,V) float32 when ``per_vertex``, else
+    None.  The keys of an error not named in ``which`` are None.  The estimates go through the kernels in chunks over N whose
+    per-vertex values stay under ``chunk_bytes``; every chunking gives the same bits.  No symmetry set enters: ADD-S needs none."""
+    dev = est.device if torch.is_tensor(est) else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    e = _f32(est, dev, "est", (None, 4, 4))
+    N = e.shape[0]
+    g = _f32(gt, dev, "gt", (N, 4, 4))
+    v = _f32(vertices, dev, "vertices", (None, 3))
+    V = v.shape[0]
+    which = tuple(which)
+    if V < 1 or any(w not in ("add", "adds") for w in which):
+        raise ValueError(f"add_errors: at least one vertex and which within ('add', 'adds') expected, got V = {V}, which = {which}")
+    kernels = N > 0 and policy.current().bop_eval == "1" and policy.guard("eval.add_errors", cuda=e.is_cuda,
+                                                                         have=ops.have("add_errors") and ops.have("adds_errors"))
+    step = max(1, min(int(chunk_bytes) // (4 * V), (2 ** 31 - 1) // V))
+    parts = []
+    for i in range(0, N, step):
+        if kernels:
+            parts.append(ops.add_errors(v, e[i:i + step], g[i:i + step], per_vertex=per_vertex, which=which))
+        else:
+            parts.append(_add_errors_library(v, e[i:i + step], g[i:i + step], which, chunk_bytes=min(int(chunk_bytes), 1 << 26)))
+    out = dict(add=None, add_max=None, add_per_vertex=None, adds=None, adds_max=None, adds_per_vertex=None)
+    for w in which:
+        for key, dtype, shape in ((w, torch.float64, (0,)), (w + "_max", torch.float32, (0,)), (w + "_per_vertex", torch.float32, (0, V))):
+            if per_vertex or key != w + "_per_vertex":
+                out[key] = torch.cat([p[key] for p in parts]) if parts else torch.zeros(shape, dtype=dtype, device=dev)
+    return out
+
+
+def _group_ids(estimates, ground_truths):
+    """(image, object) groups of the ground truths -> (est_group (E,) with -1 for an estimate in no group, gt_group (G,), keys)."""
+    e_im, e_obj = np.asarray(estimates["im"], np.int64), np.asarray(estimates["obj"], np.int64)
+    g_im, g_obj = np.asarray(ground_truths["im"], np.int64), np.asarray(ground_truths["obj"], np.int64)
+    keys = sorted(set(zip(g_im.tolist(), g_obj.tolist())))
+    gid = {k: i for i, k in enumerate(keys)}
+    gt_group = np.array([gid[k] for k in zip(g_im.tolist(), g_obj.tolist())], np.int64)
+    est_group = np.array([gid.get(k, -1) for k in zip(e_im.tolist(), e_obj.tolist())], np.int64)
+    return est_group, gt_group, keys
+
+
+def assign_errors(errors, scores, est_group, gt_group, n_targets):
+    """One error per target instance, on the host in float64.  errors: the triple (pair_est, pair_gt, pair_error) of the computed
+    pairs, or an (E,G) array; only pairs whose estimate and ground truth share a group count.  scores (E,); est_group (E,),
+    gt_group (G,): group ids in [0, len(n_targets)) (an estimate with another id is in no group); n_targets (groups,).
+    Per group the n_targets highest-scoring estimates are kept (ties: the lower index) and visited in descending score; each takes
+    the still unmatched ground truth of its group with the lowest error (ties: the lower index).  There is no threshold: the
+    assignment does not depend on one.  -> dict(error (G,) float64, +inf for a ground truth no estimate took; estimate (G,) int64,
+    -1 there)."""
+    scores, est_group, gt_group = np.asarray(scores, np.float64), np.asarray(est_group, np.int64), np.asarray(gt_group, np.int64)
+    n_targets = np.asarray(n_targets, np.int64)
+    if isinstance(errors, tuple):
+        pe, pg, pv = (np.asarray(a) for a in errors)
+    else:
+        err = np.asarray(errors, np.float64)
+        pe, pg = np.nonzero(est_group[:, None] == gt_group[None, :])
+        pv = err[pe, pg]
+    pe, pg, pv = pe.astype(np.int64), pg.astype(np.int64), np.asarray(pv, np.float64)
+    same = est_group[pe] == gt_group[pg] if len(pe) else np.zeros(0, bool)
+    pe, pg, pv = pe[same], pg[same], np.where(np.isnan(pv[same]), np.inf, pv[same])          # a NaN error counts as +inf
+    by_est = {}
+    for i in np.lexsort((pg, pe)):
+        by_est.setdefault(int(pe[i]), []).append((int(pg[i]), float(pv[i])))
+    error = np.full(len(gt_group), np.inf)
+    taker = np.full(len(gt_group), -1, np.int64)
+    for grp in range(len(n_targets)):
+        es = np.nonzero(est_group == grp)[0]
+        es = es[np.lexsort((es, -scores[es]))][:int(n_targets[grp])]
+        for e in es:
+            best, best_err = -1, float("inf")
+            for g, x in by_est.get(int(e), ()):
+                if taker[g] < 0 and (best < 0 or x < best_err):             # by ground-truth index: the first stays on ties
+                    best, best_err = g, x
+            if best >= 0:
+                taker[best] = int(e)
+                error[best] = best_err
+    return dict(error=error, estimate=taker)
+
+
+def _recall_auc(error, threshold, auc_max):
+    """recall = #{e_k < threshold_k} / targets;  AUC = mean_k max(0, 1 - e_k / auc_max): the exact area under the step curve
+    t -> #{e_k < t} / targets on [0, auc_max], divided by auc_max.  0 for no targets."""
+    if not len(error):
+        return 0.0, 0.0
+    with np.errstate(all="ignore"):
+        return float((error < threshold).mean()), float(np.maximum(0.0, 1.0 - error / float(auc_max)).mean())
+
+
+def _is_symmetric(model):
+    if model.get("symmetric"):
+        return True
+    syms = model["symmetries"] if "symmetries" in model else symmetry_transforms(model.get("info", {}))
+    return len(syms) > 1
+
+
+@torch.no_grad()
+def add_scores(models, estimates, ground_truths, frac=0.1, auc_max=100.0, device=None):
+    """ADD, ADD-S and ADD(-S) recall and AUC of a set of estimates.  models, estimates, ground_truths as in ``bop19_scores`` (no
+    faces, no images needed); a model may carry ``symmetric=True``.  Every estimate is scored against every ground truth of its
+    (image, object) group (``add_errors``), the errors are assigned to the targets by ``assign_errors``, and from the per-target
+    errors e_k:  recall = #{e_k < frac * diameter} / targets,  AUC = mean_k max(0, 1 - e_k / auc_max)  (auc_max in model units: 100
+    is 10 cm for BOP's millimetre models).  ADD(-S) takes ADD-S for an object whose symmetry set has more than the identity (or
+    that is flagged ``symmetric``) and ADD otherwise.
+    -> dict(ADD, ADD_S, ADD_or_S: each dict(recall, auc); frac, auc_max, targets, estimates)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    est_group, gt_group, keys = _group_ids(estimates, ground_truths)
+    g_obj = np.asarray(ground_truths["obj"], np.int64)
+    e_pose = np.asarray(estimates["pose"], np.float64).reshape(-1, 4, 4)
+    g_pose = np.asarray(ground_truths["pose"], np.float64).reshape(-1, 4, 4)
+    n_targets = np.bincount(gt_group, minlength=len(keys))
+    E, G = len(est_group), len(gt_group)
+    pe, pg = np.nonzero((est_group[:, None] == gt_group[None, :]) & (est_group[:, None] >= 0)) if E and G else (np.zeros(0, np.int64),) * 2
+    err = dict(add=np.zeros(len(pe)), adds=np.zeros(len(pe)))
+    diameter, symmetric = np.zeros(G), np.zeros(G, bool)
+    for obj in sorted(set(g_obj.tolist())):
+        m = models[obj]
+        diameter[g_obj == obj] = float(m["diameter"] if "diameter" in m else m["info"]["diameter"])
+        symmetric[g_obj == obj] = _is_symmetric(m)
+        sel = np.nonzero(g_obj[pg] == obj)[0]
+        if not len(sel):
+            continue
+        r = add_errors(m["vertices"], torch.as_tensor(e_pose[pe[sel]]).to(dev).float(), g_pose[pg[sel]])
+        err["add"][sel], err["adds"][sel] = r["add"].cpu().numpy(), r["adds"].cpu().numpy()
+    scores = np.asarray(estimates["score"], np.float64)
+    per_target = {k: assign_errors((pe, pg, err[k]), scores, est_group, gt_group, n_targets)["error"] for k in ("add", "adds")}
+    per_target["add_or_s"] = assign_errors((pe, pg, np.where(symmetric[pg], err["adds"], err["add"])), scores, est_group, gt_group,
+                                           n_targets)["error"]
+    out = {}
+    for name, key in (("ADD", "add"), ("ADD_S", "adds"), ("ADD_or_S", "add_or_s")):
+        recall, auc = _recall_auc(per_target[key], float(frac) * diameter, auc_max)
+        out[name] = dict(recall=recall, auc=auc)
+    out.update(frac=float(frac), auc_max=float(auc_max), targets=int(n_targets.sum()), estimates=int(E))
+    return out
+
+
+@torch.no_grad()
+def symmetry_residuals(vertices, syms, diameter=None, device=None):
+    """Do the symmetry transforms map the mesh onto itself?  vertices (V,3), syms (S,4,4) (``symmetry_transforms``) -> dict(mean (S,)
+    float64, max (S,) float64: the mean and the maximum over the vertices of min_k |S_j v_i - v_k| -- one call of the ADD-S path with
+    est = S_j and gt = I; with a ``diameter`` also mean_fraction, max_fraction = those over the diameter).  0 for a transform that
+    maps the vertex set into itself; MSSD, MSPD and ADD-S are silently wrong for one that does not."""
+    s = np.asarray(torch.as_tensor(syms).detach().cpu().double().numpy()).reshape(-1, 4, 4)
+    dev = torch.device(device) if device is not None else (vertices.device if torch.is_tensor(vertices) else
+                                                           torch.device("cuda" if torch.cuda.is_available() else "cpu"))
+    r = add_errors(vertices, torch.as_tensor(s).to(dev).float(), np.tile(np.eye(4), (len(s), 1, 1)), which=("adds",))
+    out = dict(mean=r["adds"].cpu().numpy().astype(np.float64), max=r["adds_max"].cpu().numpy().astype(np.float64))
+    if diameter is not None:
+        out.update(mean_fraction=out["mean"] / float(diameter), max_fraction=out["max"] / float(diameter))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------- VSD

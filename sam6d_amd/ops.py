@@ -920,6 +920,43 @@ def model_diameter(vertices):
     return out
 
 
+# ------------------------------------------------------------------ ADD / ADD-S pose errors (csrc/s6d_adderr.hip)
+def add_errors(vertices, est, gts, per_vertex=False, which=("add", "adds")):
+    """vertices (V,3) f32, V >= 1, est, gts (N,4,4) f32 object -> camera: N pose pairs of ONE object -> dict
+    add, adds (N,) f64: the mean over the vertices of |E v_i - G v_i| and of min_j |E v_i - G v_j| (fixed summation order);
+    add_max, adds_max (N,) f32: the maxima (adds_max: the one-sided Hausdorff distance);
+    add_per_vertex, adds_per_vertex (N,V) f32 when ``per_vertex``, None otherwise (the values then live in a workspace)
+    (include/sam6d_hip.h: s6d_pose_err_add_f32, s6d_pose_err_adds_f32).  ``which``: the errors to compute; the keys of the other
+    are None.  No (V,V) buffer is made."""
+    _chk(vertices, torch.float32, "vertices", 2)
+    _chk(est, torch.float32, "est", 3)
+    _chk(gts, torch.float32, "gts", 3)
+    V, N = vertices.shape[0], est.shape[0]
+    if vertices.shape[1] != 3 or V < 1 or tuple(est.shape[1:]) != (4, 4) or tuple(gts.shape) != (N, 4, 4):
+        raise ValueError(f"add_errors: vertices (V,3) with V >= 1, est (N,4,4), gts (N,4,4) expected, got {tuple(vertices.shape)}, "
+                         f"{tuple(est.shape)}, {tuple(gts.shape)}")
+    if N * V >= 2 ** 31:
+        raise ValueError(f"add_errors: N * V = {N * V} (2^31 or more) is refused; chunk over N (evaluation.add_errors does)")
+    dev = vertices.device
+    out = dict(add=None, add_max=None, add_per_vertex=None, adds=None, adds_max=None, adds_per_vertex=None)
+    ws = None
+    if not per_vertex:
+        ws = torch.empty((_size("s6d_pose_err_adds_workspace_bytes", N, V) + 3) // 4, dtype=torch.float32, device=dev)
+    for name in which:
+        if name not in ("add", "adds"):
+            raise ValueError(f"add_errors: which names 'add' and 'adds', got {name!r}")
+        pv = torch.empty(N, V, dtype=torch.float32, device=dev) if per_vertex else None
+        mean = torch.empty(N, dtype=torch.float64, device=dev)
+        top = torch.empty(N, dtype=torch.float32, device=dev)
+        args = (_ptr(vertices), V, _ptr(est), _ptr(gts), N, _ptr(pv), _ptr(mean), _ptr(top), _ptr(ws), _stream())
+        if name == "add":
+            _call("s6d_pose_err_add_f32", *args)
+        else:
+            _call("s6d_pose_err_adds_f32", *args)
+        out[name], out[name + "_max"], out[name + "_per_vertex"] = mean, top, pv
+    return out
+
+
 # ------------------------------------------------------------------ pose refinement against the depth (csrc/s6d_refine.hip)
 RF_CHUNK = _lib.header_constant("S6D_RF_CHUNK")          # pixels one workgroup of the normal-equation kernel sums (its reduction order)
 RF_TERMS = 28                                            # 21 upper entries of J J^T, 6 of J r, r r
@@ -1964,6 +2001,7 @@ def have(name):
                "template_ism_crops": "s6d_template_ism_crops_f32", "render_views": "s6d_raster_views_f32", "render_views_textured": "s6d_raster_views_tex_f32",
                "render_depth": "s6d_raster_depth_f32", "pose_errors": "s6d_pose_err_mssd_mspd_f32", "vsd_counts": "s6d_vsd_counts_f32",
                "gt_visibility": "s6d_gt_visibility_f32", "model_diameter": "s6d_model_diameter_f32",
+               "add_errors": "s6d_pose_err_add_f32", "adds_errors": "s6d_pose_err_adds_f32",
                "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match",
                "small_regions": "s6d_remove_small_regions_u8",
                "rle_encode": "s6d_rle_write_u8", "rle_to_packed": "s6d_rle_to_packed", "rle_to_masks": "s6d_rle_to_masks_u8",

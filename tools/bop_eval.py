@@ -12,6 +12,11 @@ produce).  DIR: a dataset in the BOP layout --
 --derive-gt: where models_eval/models_info.json or a scene's scene_gt_info.json is absent, the diameter and the visib_fract of the
 ground truths are derived in memory from the meshes, the poses and the depth images (sam6d_amd.groundtruth; what tools/bop_gt.py
 writes); without the flag the tool behaves as described above.
+--add: the line gains ``add`` = ``evaluation.add_scores``: recall (error below --add-frac of the diameter) and AUC (thresholds up to
+--auc-max model units) of ADD, ADD-S and ADD(-S), as defined in csrc/s6d_adderr.hip and sam6d_amd/evaluation.py.
+--check-symmetries: the line gains ``symmetries`` = per object how far its symmetry transforms move the mesh off itself
+(``evaluation.symmetry_residuals``), with a warning on stderr above --sym-tol of the diameter.  Without these flags the line is
+what it was before they existed.
 Every image named in the scenes' ground truth that the result file's scenes cover is scored; depth PNGs are 16 bit, times
 ``depth_scale`` = millimetres.  Prints one JSON line.
 
@@ -100,6 +105,25 @@ def load_dataset(root, split, scenes, min_visib=0.1, derive_gt=False, device=Non
     return models, gt, images, index
 
 
+def check_symmetries(models, tol, device=None):
+    """{obj: dict(transforms, max_fraction, mean_fraction, worst, ok)}: ``evaluation.symmetry_residuals`` of every object's symmetry
+    set; a warning on stderr for an object whose largest residual exceeds ``tol`` of its diameter (MSSD, MSPD and ADD-S are wrong
+    for a transform that does not map the mesh onto itself)."""
+    from sam6d_amd import evaluation
+    out = {}
+    for obj, m in sorted(models.items()):
+        syms = m["symmetries"] if "symmetries" in m else evaluation.symmetry_transforms(m.get("info", {}))
+        r = evaluation.symmetry_residuals(m["vertices"], syms, diameter=m["diameter"], device=device)
+        worst = int(np.argmax(r["max_fraction"]))
+        ok = bool(r["max_fraction"][worst] <= tol)
+        out[str(obj)] = dict(transforms=int(len(syms)), max_fraction=float(r["max_fraction"][worst]), mean_fraction=float(r["mean_fraction"].max()),
+                             worst=worst, ok=ok)
+        if not ok:
+            print(f"bop_eval: warning: symmetry transform {worst} of object {obj} moves a vertex {r['max_fraction'][worst]:.4f} of the diameter "
+                  f"off the mesh (tolerance {tol}): MSSD, MSPD and ADD-S of this object are unreliable", file=sys.stderr)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--results", required=True)
@@ -107,6 +131,12 @@ def main(argv=None):
     ap.add_argument("--split", default="test")
     ap.add_argument("--device", default=None, help="cuda (kernels) or cpu (the torch statements); default: cuda when there is one")
     ap.add_argument("--derive-gt", action="store_true", help="derive a missing models_info.json / scene_gt_info.json in memory")
+    ap.add_argument("--add", action="store_true", help="also report ADD, ADD-S and ADD(-S): recall below --add-frac of the diameter, AUC up to --auc-max")
+    ap.add_argument("--add-frac", type=float, default=0.1)
+    ap.add_argument("--auc-max", type=float, default=100.0, help="upper end of the AUC's threshold range, model units (100 = 10 cm for millimetre models)")
+    ap.add_argument("--check-symmetries", action="store_true",
+                    help="report how far every symmetry transform of models_info.json moves the mesh off itself (evaluation.symmetry_residuals)")
+    ap.add_argument("--sym-tol", type=float, default=0.01, help="warn when a transform's largest residual exceeds this fraction of the diameter")
     a = ap.parse_args(argv)
     from sam6d_amd import evaluation
     t0 = time.time()
@@ -118,6 +148,10 @@ def main(argv=None):
     est = dict(im=np.array([index[(int(s), int(i))] for s, i in zip(res["scene"][keep], res["im"][keep])], np.int64), obj=res["obj"][keep],
                score=res["score"][keep], pose=pose)
     out = evaluation.bop19_scores(models, est, gt, images, device=a.device)
+    if a.add:
+        out["add"] = evaluation.add_scores(models, est, gt, frac=a.add_frac, auc_max=a.auc_max, device=a.device)
+    if a.check_symmetries:
+        out["symmetries"] = check_symmetries(models, a.sym_tol, a.device)
     out.update(results=os.path.basename(a.results), images=len(index), dropped_estimates=int((~keep).sum()), seconds=round(time.time() - t0, 3))
     print(json.dumps(out))
     return out
