@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 137
+#define S6D_ABI_VERSION 138
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -1038,6 +1038,41 @@ int s6d_refine_normal_eq_f64(const float *xyz, const int32_t *face, const float 
                              float min_cos, void *workspace, double *sums, int32_t *count, void *stream);
 int s6d_refine_update_f64(const double *sums, const int32_t *count, const float *poses, int T, int min_count, float damping,
                           float min_pivot, float *poses_out, int32_t *status, double *rms, void *stream);
+
+/* Overlay pictures (csrc/s6d_vis.hip): detections and poses drawn over the frame on the device.  The reference
+ * draws its two pictures on the host (ref: visualize, Instance_Segmentation_Model/run_inference_custom.py:45-77; draw_detections,
+ * Pose_Estimation_Model/utils/draw_utils.py:75-97) with cv2, skimage, scipy and distinctipy, none of which is restated: the
+ * pictures are this project's DEFINITION, stated operation by operation in the header of csrc/s6d_vis.hip, all in integers after
+ * the projection.  1 <= H, W <= 8192 (larger: S6D_EUNSUPPORTED), B >= 0 frames.
+ *
+ * s6d_vis_owner_from_masks: packed (N, ceil(H W / 64)) words of s6d_mask_pack_u8 for the detections of ALL frames; order (K) i32,
+ * K <= N: detection indices frame by frame, in rank order inside a frame; frame_start (B + 1) i64 delimits the frames in order ->
+ * owner (B,H,W) i32 = the first detection of the pixel's frame whose bit is set (its index in [0, N)), -1 for none.
+ * s6d_vis_merge_layers: depth (T,H,W) f32 and rgb (T,H,W,3) u8 of s6d_raster_views_f32, frame (T) i32, the instance index of layer
+ * t being first + t, folded into the canvas zbuf (B,H,W) f32, owner (B,H,W) i32, shade (B,H,W,3) u8 (empty: owner -1, zbuf 0,
+ * shade 0): !(z > 0) is background, the nearest z wins, at equal z the lower index: the same canvas bits for any chunking and
+ * order of the layers.
+ * s6d_vis_paint_u8: image (B,H,W,3) u8, owner -> out (B,H,W,3) u8 (must not alias image): the base (gray: one luma value in every
+ * channel), blended with alpha / 256 (0 .. 256) of colors[min(owner, n_ids - 1)] ((n_ids,3) u8) or -- shade not NULL -- of shade at
+ * the pixel, and the contours of the owner map dilated to edge_width (0 .. 4) in the edge colour.
+ * s6d_vis_project_f32: points (M,3) f32, inst (M) i32 into R (N,9), t (N,3), cams (N,4) = fx fy cx cy -> xy (M,2) i32 pixels clamped
+ * to [-8192, 8191] and valid (M) bytes (zc >= znear and a finite pixel; otherwise 0 and pixel (0, 0)).
+ * s6d_vis_draw_u8: prims (P,8) i32 = frame, x0, y0, x1, y1, size (0 .. 64), r | g << 8 | b << 16, valid, sorted by frame, frame_start
+ * (B + 1) i64 -> drawn opaque into image (B,H,W,3) in place; the covering primitive of highest index wins.  A workgroup takes the
+ * frame's primitives in chunks of S6D_VIS_DRAW_CHUNK.
+ * Every entry returns S6D_EINVAL for NULL operands (colors or shade may be NULL, not both), negative counts, alpha, edge_width or
+ * colours out of range, before any launch; nothing to do (B = 0, T = 0, M = 0, P = 0): S6D_OK. */
+#define S6D_VIS_DRAW_CHUNK 256
+int s6d_vis_owner_from_masks(const uint64_t *packed, const int32_t *order, const long *frame_start, int B, int N, long K, int H,
+                             int W, int32_t *owner, void *stream);
+int s6d_vis_merge_layers(const float *depth, const uint8_t *rgb, const int32_t *frame, int T, int first, int B, int H, int W,
+                         float *zbuf, int32_t *owner, uint8_t *shade, void *stream);
+int s6d_vis_paint_u8(const uint8_t *image, const int32_t *owner, const uint8_t *colors, const uint8_t *shade, int n_ids, int B,
+                     int H, int W, int gray, int alpha, int edge_width, int edge_r, int edge_g, int edge_b, uint8_t *out,
+                     void *stream);
+int s6d_vis_project_f32(const float *points, const int32_t *inst, const float *R, const float *t, const float *cams, long M,
+                        int N, float znear, int32_t *xy, uint8_t *valid, void *stream);
+int s6d_vis_draw_u8(const int32_t *prims, const long *frame_start, int B, long P, int H, int W, uint8_t *image, void *stream);
 
 #ifdef __cplusplus
 }

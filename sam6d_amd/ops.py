@@ -1982,6 +1982,160 @@ def project_bbox(pointcloud, poses, obj, tmpl, trans, K, H, W, frame=None):
 
 
 # ------------------------------------------------------------------ fused-op registry
+# ------------------------------------------------------------------ overlay pictures (csrc/s6d_vis.hip)
+VIS_MAX_HW = 8192
+VIS_CLAMP = (-8192, 8191)
+
+
+def _vis_size(what, H, W):
+    if not (1 <= H <= VIS_MAX_HW and 1 <= W <= VIS_MAX_HW):
+        raise ValueError(f"{what}: H and W must lie in [1, {VIS_MAX_HW}], got H = {H}, W = {W}")
+
+
+def _vis_frame_start(what, frame_start, B, total):
+    _chk(frame_start, torch.int64, "frame_start", 1)
+    if frame_start.shape[0] != B + 1:
+        raise ValueError(f"{what}: frame_start must have B + 1 = {B + 1} entries, got {frame_start.shape[0]}")
+    fs = frame_start.cpu()
+    if int(fs[0]) != 0 or int(fs[-1]) != total or bool((fs[1:] < fs[:-1]).any()):
+        raise ValueError(f"{what}: frame_start must rise from 0 to {total}, got {fs.tolist()}")
+
+
+def vis_owner_from_masks(packed, order, frame_start, H, W):
+    """packed (N, ceil(H W / 64)) int64 (``mask_pack`` / ``rle_to_packed``) of the detections of all frames, order (K,) int32 the
+    detection indices frame by frame in rank order, frame_start (B+1,) int64 -> owner (B,H,W) int32: the first detection of the
+    pixel's frame that covers it, -1 for none (include/sam6d_hip.h: s6d_vis_owner_from_masks)."""
+    H, W = int(H), int(W)
+    _vis_size("vis_owner_from_masks", H, W)
+    _chk(packed, torch.int64, "packed", 2)
+    _chk(order, torch.int32, "order", 1)
+    N, K, B = packed.shape[0], order.shape[0], frame_start.shape[0] - 1
+    if packed.shape[1] != (H * W + 63) // 64:
+        raise ValueError(f"vis_owner_from_masks: packed must have ceil(H W / 64) = {(H * W + 63) // 64} words per mask, got {packed.shape[1]}")
+    if K > N:
+        raise ValueError(f"vis_owner_from_masks: order names {K} detections, packed has {N}")
+    _vis_frame_start("vis_owner_from_masks", frame_start, B, K)
+    owner = torch.empty(B, H, W, dtype=torch.int32, device=packed.device)
+    _call("s6d_vis_owner_from_masks", _ptr(packed), _ptr(order), _ptr(frame_start), B, N, K, H, W, _ptr(owner), _stream())
+    return owner
+
+
+def vis_canvas(B, H, W, device):
+    """The empty canvas of ``vis_merge_layers``: dict(zbuf (B,H,W) f32 = 0, owner (B,H,W) int32 = -1, shade (B,H,W,3) uint8 = 0)."""
+    return dict(zbuf=torch.zeros(B, H, W, dtype=torch.float32, device=device), owner=torch.full((B, H, W), -1, dtype=torch.int32, device=device),
+                shade=torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device))
+
+
+def vis_merge_layers(canvas, depth, rgb, frame, first):
+    """Folds the layers depth (T,H,W) f32, rgb (T,H,W,3) uint8 (``render_views``) of the instances first .. first + T - 1, layer t
+    belonging to frame[t] ((T,) int32), into ``canvas`` (``vis_canvas``) IN PLACE: the nearest z > 0 wins, at equal z the lower
+    instance index (include/sam6d_hip.h: s6d_vis_merge_layers).  A frame outside [0, B) is refused here, on the host."""
+    _chk(depth, torch.float32, "depth", 3)
+    _chk(rgb, torch.uint8, "rgb", 4)
+    _chk(frame, torch.int32, "frame", 1)
+    _chk(canvas["zbuf"], torch.float32, "zbuf", 3)
+    _chk(canvas["owner"], torch.int32, "owner", 3)
+    _chk(canvas["shade"], torch.uint8, "shade", 4)
+    T, H, W = depth.shape
+    B = canvas["zbuf"].shape[0]
+    _vis_size("vis_merge_layers", H, W)
+    if (tuple(rgb.shape) != (T, H, W, 3) or frame.shape[0] != T or tuple(canvas["zbuf"].shape) != (B, H, W)
+            or tuple(canvas["owner"].shape) != (B, H, W) or tuple(canvas["shade"].shape) != (B, H, W, 3)):
+        raise ValueError(f"vis_merge_layers: depth (T,H,W), rgb (T,H,W,3), frame (T,) and a canvas of (B,H,W) expected, got "
+                         f"{tuple(depth.shape)}, {tuple(rgb.shape)}, {tuple(frame.shape)}, {tuple(canvas['zbuf'].shape)}")
+    if T and (int(frame.min()) < 0 or int(frame.max()) >= B):
+        raise ValueError(f"vis_merge_layers: frame must lie in [0, {B}), got [{int(frame.min())}, {int(frame.max())}]")
+    if int(first) < 0:
+        raise ValueError(f"vis_merge_layers: first must be >= 0, got {first}")
+    _call("s6d_vis_merge_layers", _ptr(depth), _ptr(rgb), _ptr(frame), T, int(first), B, H, W, _ptr(canvas["zbuf"]), _ptr(canvas["owner"]),
+          _ptr(canvas["shade"]), _stream())
+    return canvas
+
+
+def vis_paint(image, owner, colors=None, shade=None, alpha=84, gray=True, edge_width=2, edge_color=(255, 255, 255)):
+    """image (B,H,W,3) uint8, owner (B,H,W) int32 and either colors (n_ids,3) uint8 or shade (B,H,W,3) uint8 -> the painted picture
+    (B,H,W,3) uint8: base (grey or as it is), alpha / 256 of the owner's colour, contours of the owner map in edge_color dilated to
+    edge_width (include/sam6d_hip.h: s6d_vis_paint_u8)."""
+    _chk(image, torch.uint8, "image", 4)
+    _chk(owner, torch.int32, "owner", 3)
+    B, H, W, _ = image.shape
+    _vis_size("vis_paint", H, W)
+    if image.shape[3] != 3 or tuple(owner.shape) != (B, H, W):
+        raise ValueError(f"vis_paint: image (B,H,W,3) and owner (B,H,W) expected, got {tuple(image.shape)}, {tuple(owner.shape)}")
+    if (colors is None) == (shade is None):
+        raise ValueError("vis_paint: exactly one of colors and shade is needed")
+    if not 0 <= int(alpha) <= 256:
+        raise ValueError(f"vis_paint: alpha must lie in [0, 256] (units of 1/256), got {alpha}")
+    if not 0 <= int(edge_width) <= 4:
+        raise ValueError(f"vis_paint: edge_width must lie in [0, 4], got {edge_width}")
+    edge = [int(c) for c in edge_color]
+    if len(edge) != 3 or min(edge) < 0 or max(edge) > 255:
+        raise ValueError(f"vis_paint: edge_color must be three values in [0, 255], got {edge_color}")
+    n_ids = 0
+    if colors is not None:
+        _chk(colors, torch.uint8, "colors", 2)
+        n_ids = colors.shape[0]
+        if n_ids < 1 or colors.shape[1] != 3:
+            raise ValueError(f"vis_paint: colors (n_ids,3) with n_ids >= 1 expected, got {tuple(colors.shape)}")
+    else:
+        _chk(shade, torch.uint8, "shade", 4)
+        if tuple(shade.shape) != (B, H, W, 3):
+            raise ValueError(f"vis_paint: shade {(B, H, W, 3)} expected, got {tuple(shade.shape)}")
+    out = torch.empty_like(image)
+    _call("s6d_vis_paint_u8", _ptr(image), _ptr(owner), _ptr(colors), _ptr(shade), n_ids, B, H, W, 1 if gray else 0, int(alpha),
+          int(edge_width), edge[0], edge[1], edge[2], _ptr(out), _stream())
+    return out
+
+
+def vis_project(points, inst, R, t, cams, znear):
+    """points (M,3) f32, inst (M,) int32 into R (N,3,3) f32, t (N,3) f32, cams (N,4) f32 = fx fy cx cy -> (xy (M,2) int32 pixels
+    clamped to [-8192, 8191], valid (M,) uint8) (include/sam6d_hip.h: s6d_vis_project_f32)."""
+    _chk(points, torch.float32, "points", 2)
+    _chk(inst, torch.int32, "inst", 1)
+    _chk(R, torch.float32, "R", 3)
+    _chk(t, torch.float32, "t", 2)
+    _chk(cams, torch.float32, "cams", 2)
+    M, N = points.shape[0], R.shape[0]
+    if points.shape[1] != 3 or inst.shape[0] != M or tuple(R.shape[1:]) != (3, 3) or tuple(t.shape) != (N, 3) or tuple(cams.shape) != (N, 4):
+        raise ValueError(f"vis_project: points (M,3), inst (M,), R (N,3,3), t (N,3), cams (N,4) expected, got {tuple(points.shape)}, "
+                         f"{tuple(inst.shape)}, {tuple(R.shape)}, {tuple(t.shape)}, {tuple(cams.shape)}")
+    xy = torch.empty(M, 2, dtype=torch.int32, device=points.device)
+    valid = torch.empty(M, dtype=torch.uint8, device=points.device)
+    _call("s6d_vis_project_f32", _ptr(points), _ptr(inst), _ptr(R), _ptr(t), _ptr(cams), M, N, float(znear), _ptr(xy), _ptr(valid), _stream())
+    return xy, valid
+
+
+def vis_draw_chunk():
+    """How many primitives a workgroup of the draw kernel takes at a time (S6D_VIS_DRAW_CHUNK of include/sam6d_hip.h)."""
+    return _lib.header_constant("S6D_VIS_DRAW_CHUNK")
+
+
+def vis_draw(image, prims, frame_start, check=True):
+    """Draws prims (P,8) int32 = frame, x0, y0, x1, y1, size, r | g << 8 | b << 16, valid -- sorted by frame, frame_start (B+1,)
+    int64 -- opaque into image (B,H,W,3) uint8 IN PLACE; the covering primitive of highest index wins (include/sam6d_hip.h:
+    s6d_vis_draw_u8).  check (it reads the device: a synchronisation) refuses a size outside [0, 64], a frame that is not the one
+    frame_start files the entry under, and a coordinate of a valid entry outside [-8192, 8191]."""
+    _chk(image, torch.uint8, "image", 4)
+    _chk(prims, torch.int32, "prims", 2)
+    B, H, W, _ = image.shape
+    _vis_size("vis_draw", H, W)
+    P = prims.shape[0]
+    if image.shape[3] != 3 or prims.shape[1] != 8:
+        raise ValueError(f"vis_draw: image (B,H,W,3) and prims (P,8) expected, got {tuple(image.shape)}, {tuple(prims.shape)}")
+    _vis_frame_start("vis_draw", frame_start, B, P)
+    if check and P:
+        if int(prims[:, 5].min()) < 0 or int(prims[:, 5].max()) > 64:
+            raise ValueError(f"vis_draw: size must lie in [0, 64], got [{int(prims[:, 5].min())}, {int(prims[:, 5].max())}]")
+        want = torch.repeat_interleave(torch.arange(B, device=prims.device), (frame_start[1:] - frame_start[:-1]))
+        if bool((prims[:, 0] != want).any()):
+            raise ValueError(f"vis_draw: frame must lie in [0, {B}) and the list be sorted by it as frame_start says")
+        xy = prims[:, 1:5][prims[:, 7] != 0]
+        if xy.numel() and (int(xy.min()) < VIS_CLAMP[0] or int(xy.max()) > VIS_CLAMP[1]):
+            raise ValueError(f"vis_draw: coordinates must lie in [{VIS_CLAMP[0]}, {VIS_CLAMP[1]}], got [{int(xy.min())}, {int(xy.max())}]")
+    _call("s6d_vis_draw_u8", _ptr(prims), _ptr(frame_start), B, P, H, W, _ptr(image), _stream())
+    return image
+
+
 # Names of fused gfx950 ops the loaded library exports.  Product modules ask ``have(name)``
 # and otherwise express the same math with library GEMMs on the device (never on the CPU).
 _FUSED = {}
@@ -2005,7 +2159,9 @@ def have(name):
                "mask_pack": "s6d_mask_pack_u8", "mask_pair_inter": "s6d_mask_pair_inter", "box_pair_iou": "s6d_box_pair_iou_f64", "coco_match": "s6d_coco_match",
                "small_regions": "s6d_remove_small_regions_u8",
                "rle_encode": "s6d_rle_write_u8", "rle_to_packed": "s6d_rle_to_packed", "rle_to_masks": "s6d_rle_to_masks_u8",
-               "refine_normal_eq": "s6d_refine_normal_eq_f64", "refine_update": "s6d_refine_update_f64"}.get(name)
+               "refine_normal_eq": "s6d_refine_normal_eq_f64", "refine_update": "s6d_refine_update_f64",
+               "vis_owner_from_masks": "s6d_vis_owner_from_masks", "vis_merge_layers": "s6d_vis_merge_layers", "vis_paint": "s6d_vis_paint_u8",
+               "vis_project": "s6d_vis_project_f32", "vis_draw": "s6d_vis_draw_u8"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):
