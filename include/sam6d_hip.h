@@ -33,7 +33,7 @@ extern "C" {
  * s6d_*_workspace_bytes function returns -- s6d_fine_match_workspace_bytes grew with the background exponentials -- which is safe
  * only because a caller must size the buffer through that function of the very library it calls, never from a formula of its own); the loader (sam6d_amd/_lib.py) refuses a library whose
  * s6d_version() differs from the header it was written against (a stale .so fails at load, not at a call). */
-#define S6D_ABI_VERSION 138
+#define S6D_ABI_VERSION 139
 int s6d_version(void);
 /* Upper bound on the workgroups of the persistent kernels (the 14 x 14 window attention walks its (window, head) items with one
  * workgroup per CU); 0 = one per CU of the device.  Process-wide.  Replaces the environment lookups the launch path made until
@@ -1073,6 +1073,35 @@ int s6d_vis_paint_u8(const uint8_t *image, const int32_t *owner, const uint8_t *
 int s6d_vis_project_f32(const float *points, const int32_t *inst, const float *R, const float *t, const float *cams, long M,
                         int N, float znear, int32_t *xy, uint8_t *valid, void *stream);
 int s6d_vis_draw_u8(const int32_t *prims, const long *frame_start, int B, long P, int H, int W, uint8_t *image, void *stream);
+
+/* Pose verification against the measured depth (csrc/s6d_verify.hip): per-pose evidence counts and a per-frame
+ * selection in which a measured pixel supports at most one kept pose.  SAM-6D has no such step (no ref) and no other tool's is
+ * restated: the step is this project's DEFINITION, stated operation by operation in the header of csrc/s6d_verify.hip -- two float32
+ * operations per pixel, integers after that: the same result alone, in a batch and under any scheduling.
+ *
+ * s6d_verify_evidence_f32: render (N,H,W) f32 = s6d_raster_depth_f32 of every instance (camera Z in model units, 0 = background);
+ * depth_obs (M,H,W) f32 measured depth, depth_unit model units per unit of it; obs_index (N) i32 into M (outside: the instance's
+ * rendered pixels all count as missing); masks (N,H,W) bytes or NULL; tau in model units -> counts (N,8) i32 = rendered, missing,
+ * inlier (|depth_obs depth_unit - render| <= tau), occluded, behind, det, det && rendered, det && inlier; inlier (N, ceil(H W / 64))
+ * words in the layout of s6d_mask_pack_u8; span (N,2) i32 = first and last non-zero word, (words, -1) for none.
+ * s6d_verify_select: inlier, counts, span of the above; order (K) i32, K <= N: instance indices frame by frame in visiting order;
+ * frame_start (B + 1) i64; flagged (N) bytes or NULL -> status (N) i32 and fresh (N) i32 = the instance's inlier pixels no kept
+ * instance visited before it in its frame had: 4 = nothing rendered or flagged (and every instance order does not name, fresh 0),
+ * 1 = inlier < min_inliers, 2 = inlier < min_fit (inlier + behind), 3 = fresh < min_fresh inlier (products and compares in double),
+ * 0 = kept.  One workgroup per frame; its bitmap of claimed pixels lives in LDS up to S6D_VERIFY_LDS_WORDS words a frame (or what
+ * s6d_set_verify_lds_words(w), 0 = the default, lowered that to -- for the tests; same results) and otherwise in workspace:
+ * s6d_verify_select_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: workspace may be NULL; -1 for sizes the entry refuses).
+ * Both return S6D_EINVAL for NULL operands (masks, flagged excepted), M, H or W < 1, negative counts, K > N, depth_unit not positive
+ * and finite, tau, min_fit or min_fresh negative or NaN, min_inliers < 0, and S6D_EUNSUPPORTED for H W >= 2^29, before any launch;
+ * N = 0: S6D_OK. */
+#define S6D_VERIFY_LDS_WORDS 4800
+int s6d_set_verify_lds_words(int words);
+int s6d_verify_evidence_f32(const float *render, const float *depth_obs, const int32_t *obs_index, const uint8_t *masks, int N, int M,
+                            int H, int W, float depth_unit, float tau, int32_t *counts, uint64_t *inlier, int32_t *span, void *stream);
+long s6d_verify_select_workspace_bytes(int B, int H, int W);
+int s6d_verify_select(const uint64_t *inlier, const int32_t *counts, const int32_t *span, const int32_t *order,
+                      const long *frame_start, const uint8_t *flagged, int B, int N, long K, int H, int W, int min_inliers,
+                      float min_fit, float min_fresh, void *workspace, int32_t *status, int32_t *fresh, void *stream);
 
 #ifdef __cplusplus
 }

@@ -800,10 +800,11 @@ def render_views_textured(vertices, faces, uv, pyramid, poses, fx, fy, cx, cy, H
     return out
 
 
-def render_depth(vertices, faces, poses, cams, H, W, znear):
+def render_depth(vertices, faces, poses, cams, H, W, znear, check_faces=True):
     """vertices (V,3) f32, faces (F,3) int32, poses (T,4,4) f32 object -> camera, cams (T,4) f32 = fx fy cx cy per view ->
     dict(depth (T,H,W) f32 camera Z, 0 on background; skipped (T,) int32): the depth bits of ``render_views`` for the same view and
-    camera (include/sam6d_hip.h: s6d_raster_depth_f32).  A face index outside [0, V) is refused here, on the host."""
+    camera (include/sam6d_hip.h: s6d_raster_depth_f32).  A face index outside [0, V) is refused here, on the host (check_faces=False
+    skips that read of the device: for a caller that checked the mesh once, as ``render_views`` allows)."""
     _chk(vertices, torch.float32, "vertices", 2)
     _chk(faces, torch.int32, "faces", 2)
     _chk(poses, torch.float32, "poses", 3)
@@ -812,7 +813,7 @@ def render_depth(vertices, faces, poses, cams, H, W, znear):
     if vertices.shape[1] != 3 or faces.shape[1] != 3 or tuple(poses.shape[1:]) != (4, 4) or tuple(cams.shape) != (T, 4):
         raise ValueError(f"render_depth: vertices (V,3), faces (F,3), poses (T,4,4), cams (T,4) expected, got {tuple(vertices.shape)}, "
                          f"{tuple(faces.shape)}, {tuple(poses.shape)}, {tuple(cams.shape)}")
-    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+    if check_faces and F and (int(faces.min()) < 0 or int(faces.max()) >= V):
         raise ValueError(f"render_depth: face indices must lie in [0, {V}), got [{int(faces.min())}, {int(faces.max())}]")
     nbytes = _size("s6d_raster_depth_workspace_bytes", T, F, H, W)
     if nbytes < 0:
@@ -2136,6 +2137,106 @@ def vis_draw(image, prims, frame_start, check=True):
     return image
 
 
+# ------------------------------------------------------------------ pose verification (csrc/s6d_verify.hip)
+def _verify_size(what, H, W):
+    if H < 1 or W < 1 or H * W >= 2 ** 29:
+        raise ValueError(f"{what}: H, W >= 1 and H W < 2^29 expected, got H = {H}, W = {W}")
+
+
+def set_verify_lds_words(words):
+    """The largest claimed bitmap (words of 64 pixels per frame) ``verify_select`` keeps in LDS; 0 = the default, 4800
+    (include/sam6d_hip.h: s6d_set_verify_lds_words): lets tests reach the workspace path at small shapes; same results for every
+    setting."""
+    _call("s6d_set_verify_lds_words", int(words))
+
+
+def verify_evidence(render, depth_obs, obs_index, depth_unit, tau, masks=None, check=True):
+    """render (N,H,W) f32 = ``render_depth`` of every instance (camera Z in model units, 0 on background), depth_obs (M,H,W) f32
+    measured depth, obs_index (N,) int32 into M, depth_unit model units per unit of depth_obs, tau model units, masks (N,H,W) uint8
+    or None -> dict(counts (N,8) int32 = rendered, missing, inlier, occluded, behind, det, det and rendered, det and inlier;
+    inlier (N, ceil(H W / 64)) int64 in the word layout of ``mask_pack``; span (N,2) int32 = first and last non-zero word,
+    (words, -1) for none) (include/sam6d_hip.h: s6d_verify_evidence_f32).  An obs_index outside [0, M) is refused here, on the host
+    (check=False skips that read of the device; such an instance then counts every rendered pixel as missing)."""
+    _chk(render, torch.float32, "render", 3)
+    _chk(depth_obs, torch.float32, "depth_obs", 3)
+    _chk(obs_index, torch.int32, "obs_index", 1)
+    N, H, W = render.shape
+    M = depth_obs.shape[0]
+    if M < 1 or tuple(depth_obs.shape[1:]) != (H, W) or tuple(obs_index.shape) != (N,):
+        raise ValueError(f"verify_evidence: render (N,H,W), depth_obs (M,H,W), obs_index (N,) expected, got {tuple(render.shape)}, "
+                         f"{tuple(depth_obs.shape)}, {tuple(obs_index.shape)}")
+    _verify_size("verify_evidence", H, W)
+    if masks is not None:
+        _chk(masks, torch.uint8, "masks", 3)
+        if tuple(masks.shape) != (N, H, W):
+            raise ValueError(f"verify_evidence: masks {(N, H, W)} expected, got {tuple(masks.shape)}")
+    unit, tau = float(torch.tensor(float(depth_unit), dtype=torch.float32)), float(torch.tensor(float(tau), dtype=torch.float32))
+    if not (0 < unit < float("inf")) or not tau >= 0:
+        raise ValueError(f"verify_evidence: depth_unit must be positive and finite and tau >= 0, got {depth_unit}, {tau}")
+    if check and N and (int(obs_index.min()) < 0 or int(obs_index.max()) >= M):
+        raise ValueError(f"verify_evidence: obs_index must lie in [0, {M}), got [{int(obs_index.min())}, {int(obs_index.max())}]")
+    dev, words = render.device, (H * W + 63) // 64
+    out = dict(counts=torch.empty(N, 8, dtype=torch.int32, device=dev), inlier=torch.empty(N, words, dtype=torch.int64, device=dev),
+               span=torch.empty(N, 2, dtype=torch.int32, device=dev))
+    _call("s6d_verify_evidence_f32", _ptr(render), _ptr(depth_obs), _ptr(obs_index), _ptr(masks), N, M, H, W, unit, tau,
+          _ptr(out["counts"]), _ptr(out["inlier"]), _ptr(out["span"]), _stream())
+    return out
+
+
+def verify_select(inlier, counts, span, order, frame_start, flagged, min_inliers, min_fit, min_fresh, H=None, W=None, check=True):
+    """inlier, counts, span of ``verify_evidence``; order (K,) int32 the instance indices frame by frame in visiting order,
+    frame_start (B+1,) int64; flagged (N,) uint8 / bool or None -> (status (N,) int32, fresh (N,) int32): per frame a pixel supports at
+    most one kept instance (include/sam6d_hip.h: s6d_verify_select; 0 kept, 1 too few inliers, 2 fit below min_fit, 3 explained
+    already, 4 not verifiable or not named in order).  H, W: the image size, checked against the word count when given; the kernel
+    needs the word count only, so the default is any image of that many words.  An order outside [0, N) or naming an instance twice and
+    a frame_start that does not rise from 0 to K are refused here, on the host (check=False skips those reads of the device)."""
+    _chk(inlier, torch.int64, "inlier", 2)
+    _chk(counts, torch.int32, "counts", 2)
+    _chk(span, torch.int32, "span", 2)
+    _chk(order, torch.int32, "order", 1)
+    N, words = inlier.shape
+    K, B = order.shape[0], frame_start.shape[0] - 1
+    if tuple(counts.shape) != (N, 8) or tuple(span.shape) != (N, 2) or words < 1:
+        raise ValueError(f"verify_select: inlier (N,words), counts (N,8), span (N,2) expected, got {tuple(inlier.shape)}, "
+                         f"{tuple(counts.shape)}, {tuple(span.shape)}")
+    if H is None or W is None:
+        H, W = 1, 64 * words - 63
+    H, W = int(H), int(W)
+    _verify_size("verify_select", H, W)
+    if (H * W + 63) // 64 != words:
+        raise ValueError(f"verify_select: inlier must have ceil(H W / 64) = {(H * W + 63) // 64} words per instance, got {words}")
+    if K > N:
+        raise ValueError(f"verify_select: order names {K} instances, inlier has {N}")
+    if flagged is not None:
+        flagged = flagged.to(torch.uint8) if flagged.dtype == torch.bool else flagged
+        _chk(flagged, torch.uint8, "flagged", 1)
+        if flagged.shape[0] != N:
+            raise ValueError(f"verify_select: flagged ({N},) expected, got {tuple(flagged.shape)}")
+    mi, mf, mr = int(min_inliers), float(min_fit), float(min_fresh)
+    if mi < 0 or not mf >= 0 or not mr >= 0:
+        raise ValueError(f"verify_select: min_inliers, min_fit and min_fresh must be >= 0, got {min_inliers}, {min_fit}, {min_fresh}")
+    if check:
+        _vis_frame_start("verify_select", frame_start, B, K)
+        if K and (int(order.min()) < 0 or int(order.max()) >= N):
+            raise ValueError(f"verify_select: order must lie in [0, {N}), got [{int(order.min())}, {int(order.max())}]")
+        if K and int(torch.unique(order).numel()) != K:
+            raise ValueError("verify_select: order names an instance more than once")
+    else:
+        _chk(frame_start, torch.int64, "frame_start", 1)
+        if B < 0:
+            raise ValueError("verify_select: frame_start must have B + 1 entries")
+    dev = inlier.device
+    nbytes = _size("s6d_verify_select_workspace_bytes", B, H, W)
+    if nbytes < 0:
+        raise RuntimeError(f"verify_select: unsupported sizes (B {B}, H {H}, W {W})")
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev) if nbytes else None
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    fresh = torch.empty(N, dtype=torch.int32, device=dev)
+    _call("s6d_verify_select", _ptr(inlier), _ptr(counts), _ptr(span), _ptr(order), _ptr(frame_start), _ptr(flagged), B, N, K, H, W, mi,
+          mf, mr, _ptr(ws), _ptr(status), _ptr(fresh), _stream())
+    return status, fresh
+
+
 # Names of fused gfx950 ops the loaded library exports.  Product modules ask ``have(name)``
 # and otherwise express the same math with library GEMMs on the device (never on the CPU).
 _FUSED = {}
@@ -2161,7 +2262,8 @@ def have(name):
                "rle_encode": "s6d_rle_write_u8", "rle_to_packed": "s6d_rle_to_packed", "rle_to_masks": "s6d_rle_to_masks_u8",
                "refine_normal_eq": "s6d_refine_normal_eq_f64", "refine_update": "s6d_refine_update_f64",
                "vis_owner_from_masks": "s6d_vis_owner_from_masks", "vis_merge_layers": "s6d_vis_merge_layers", "vis_paint": "s6d_vis_paint_u8",
-               "vis_project": "s6d_vis_project_f32", "vis_draw": "s6d_vis_draw_u8"}.get(name)
+               "vis_project": "s6d_vis_project_f32", "vis_draw": "s6d_vis_draw_u8",
+               "verify_evidence": "s6d_verify_evidence_f32", "verify_select": "s6d_verify_select"}.get(name)
         _FUSED[name] = sym is not None and hasattr(_lib.lib(), sym)
     # (policy.disable_fused: kernel names the modules must not use -- the tests' way of forcing the library statement)
     if policy.current().disable_fused and name in policy.current().disable_fused.split(","):

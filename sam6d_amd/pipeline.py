@@ -32,7 +32,7 @@ from .sam.transforms import ResizeLongestSide
 class FramePipeline:
     def __init__(self, sam_encoder, prompt_encoder, mask_decoder, descriptor_model, scorer, pem_net, pem_templates,
                  object_radius, top_k=10, points_per_batch=1024, min_box_size=0.05 ** 2, min_mask_size=3e-4,
-                 segmentor=None, nms_per_object_thresh=None, det_score_thresh=None, sync_stages=True, refiner=None):
+                 segmentor=None, nms_per_object_thresh=None, det_score_thresh=None, sync_stages=True, refiner=None, verifier=None):
         """descriptor_model: sam6d_amd.ism.dinov2.CustomDINOv2; scorer: sam6d_amd.ism.scoring.FrameScorer (holds the
         template descriptors); pem_templates: dict(dense_po (O,n,3), dense_fo (O,n,C), model (O,m,3)) of the O objects (O = 1: every detection
         is that object; O > 1: rows are picked by the ISM's predicted object id); object_radius: a number or an (O,) tensor;
@@ -56,6 +56,7 @@ class FramePipeline:
         self.times = {}
         self.sync_stages = sync_stages
         self.refiner = refiner
+        self.verifier = verifier                                   # pem.verify.PoseVerifier: judges the poses, drops no row
         self.graph_max = int(policy.current().pem_graph_max)      # instance counts up to this one replay a captured graph
         self._pem_graphs = {}
         # a captured graph bakes the weights' addresses and derived buffers in: the fingerprint in _pem_graph_key sees version bumps and
@@ -287,8 +288,12 @@ class FramePipeline:
         t0 = self._tick("pem", t0)
         if self.refiner is not None:
             out = self._refine(out, dets, frames, count, obs_l, oid if multi else None)
-            self._tick("pem_refine", t0)
-        extra = [key for key in ("pred_R_pem", "pred_t_pem", "refine_status", "refine_rms") if key in out]
+            t0 = self._tick("pem_refine", t0)
+        if self.verifier is not None:
+            out = self._verify(out, dets, frames, count, obs_l, oid if multi else None)
+            self._tick("pem_verify", t0)
+        extra = [key for key in ("pred_R_pem", "pred_t_pem", "refine_status", "refine_rms", "verify_keep", "verify_status", "verify_score")
+                 if key in out]
         res, at, k = [], 0, 0
         for det, n in zip(dets, count):
             if n == 0:
@@ -322,6 +327,28 @@ class FramePipeline:
             at += n
             k += 1
         return dict(out, pred_R=R, pred_t=t, pred_R_pem=out["pred_R"], pred_t_pem=out["pred_t"], refine_status=status, refine_rms=rms)
+
+    def _verify(self, out, dets, frames, count, obs_l, oid):
+        """The poses of the group (the refined ones when there is a refiner) judged against each frame's own depth map
+        (pem/verify.py): per frame one call of the verifier with that frame's depth and camera, the instances' object ids and --
+        ``verifier.use_masks`` -- the kept detections' masks.  -> ``out`` with verify_keep, verify_status and verify_score per
+        instance; no row is dropped and pred_pose_score stays the PEM's."""
+        R, t = out["pred_R"].float(), out["pred_t"].float()
+        keep = torch.zeros(R.shape[0], dtype=torch.bool, device=R.device)
+        status = torch.zeros(R.shape[0], dtype=torch.int32, device=R.device)
+        score = torch.zeros(R.shape[0], dtype=torch.float64, device=R.device)
+        at, k = 0, 0
+        for det, frame, n in zip(dets, frames, count):
+            if n == 0:
+                continue
+            sl = slice(at, at + n)
+            masks = det.masks[obs_l[k]["kept"]] if getattr(self.verifier, "use_masks", False) else None
+            ver = self.verifier([0] * n if oid is None else oid[sl], R[sl].contiguous(), t[sl].contiguous(), frame[1].float(), frame[2],
+                                masks=masks)
+            keep[sl], status[sl], score[sl] = ver["keep"], ver["status"], ver["score"]
+            at += n
+            k += 1
+        return dict(out, verify_keep=keep, verify_status=status, verify_score=score)
 
 
 def frame_results(det, poses, dataset_name, time_s=0.0):
