@@ -505,6 +505,13 @@ __global__ __launch_bounds__(64) void masked_depth_final_kernel(const float *__r
   }
 }
 
+// `.to(torch.int)` of the pinned (x86) run, spelled out: a value inside the int range is truncated toward zero, everything
+// else (NaN, +-inf, |x| >= 2^31) becomes INT_MIN -- the "integer indefinite" of the x86 conversion.  A bare (int) cast is
+// undefined there in C++, and the device's conversion saturates (+inf -> INT_MAX, NaN -> 0) instead.
+__device__ __forceinline__ int trunc_to_int_pinned(float x) {
+  return (x >= -2147483648.f && x < 2147483648.f) ? (int)x : (-2147483647 - 1);
+}
+
 // Rotate the object's model points by the best template pose, translate, project with K, truncate to
 // pixels, clamp, and reduce the per-proposal bounding box (detector.py:209-232 + :316-318).
 __global__ __launch_bounds__(256) void project_bbox_kernel(const float *__restrict__ pointcloud, const float *__restrict__ poses,
@@ -530,7 +537,7 @@ __global__ __launch_bounds__(256) void project_bbox_kernel(const float *__restri
     const float hx = __fmaf_rn(K[2], pz, __fmaf_rn(K[1], py, __fmul_rn(K[0], px)));
     const float hy = __fmaf_rn(K[5], pz, __fmaf_rn(K[4], py, __fmul_rn(K[3], px)));
     const float hz = __fmaf_rn(K[8], pz, __fmaf_rn(K[7], py, __fmul_rn(K[6], px)));
-    int u = (int)__fdiv_rn(hx, hz), v = (int)__fdiv_rn(hy, hz);   // .to(torch.int): truncation toward zero
+    int u = trunc_to_int_pinned(__fdiv_rn(hx, hz)), v = trunc_to_int_pinned(__fdiv_rn(hy, hz));   // .to(torch.int)
     u = min(max(u, 0), W - 1);
     v = min(max(v, 0), H - 1);
     uv[((size_t)s * N + i) * 2] = u;

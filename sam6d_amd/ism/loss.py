@@ -33,7 +33,7 @@ class PairwiseSimilarity(nn.Module):
         """query (P,C), reference (O,T,C) -> (P,O,T) in [0,1]."""
         O, T, C = reference.shape
         if policy.guard("ism.PairwiseSimilarity", cuda=query.is_cuda, have=ops.have("pairwise_cosine"),
-                        float_dtypes=query.dtype in _FLOATS and reference.dtype in _FLOATS):
+                        float_dtypes=query.dtype in _FLOATS and reference.dtype in _FLOATS, C16=C % 16 == 0):
             # fp16 / bf16 descriptors (the BOP flow runs under Lightning precision=16, configs/machine/trainer/local.yaml:9) take
             # the same kernel: it accumulates in fp32 either way, and under autocast the reference's cosine_similarity is an
             # fp32 op with an fp32 result -- which is what comes back here

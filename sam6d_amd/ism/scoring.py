@@ -30,7 +30,9 @@ def masked_depth_translation(masks, depth, K, depth_scale):
     """Mean back-projected point of each mask (utils/trimesh_utils.py:77-105 applied to
     mask*depth, detector.py:234-246) without the (S,H,W) ``repeat``: three masked sums."""
     S, H, W = masks.shape
-    if policy.guard("ism.masked_depth_mean", cuda=masks.is_cuda, have=ops.have("masked_depth_mean")):
+    # the kernel reads the maps as float4 and follows ATen's 16-row cascade, which holds for 8 <= H*W < 2^24 (csrc/s6d_ism.hip)
+    if policy.guard("ism.masked_depth_mean", cuda=masks.is_cuda, have=ops.have("masked_depth_mean"), W4=W % 4 == 0,
+                    pixels_8_to_2p24=8 <= H * W < 2 ** 24):
         return ops.masked_depth_mean(masks.to(torch.float32).contiguous(), depth.to(torch.float32).contiguous(), K,
                                      float(depth_scale))
     # dtype trail of the reference: Z float32; X, Y float64 (the camera matrix is a float64 tensor
@@ -100,7 +102,7 @@ class ScoringMixin:
         thred = getattr(self, "visible_thred", 0.5)
         halfs = (torch.float16, torch.bfloat16)
         if policy.guard("ism.compute_appearance_score", cuda=qurey_appe_descriptors.is_cuda, have=ops.have("patch_scores"),
-                        contiguous_store=store.is_contiguous(), patches_le_256=store.shape[2] <= 256,
+                        contiguous_store=store.is_contiguous(), patches_le_256=store.shape[2] <= 256, C32=store.shape[-1] % 32 == 0,
                         dtypes=store.dtype in (torch.float32,) + halfs and qurey_appe_descriptors.dtype in (torch.float32,) + halfs):
             # half descriptors (BOP flow under precision=16): the resident store is converted ONCE per store tensor and kept (it
             # is read-only template data); the query of the frame is converted per call.  fp32 arithmetic inside the kernel.
